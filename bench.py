@@ -1,6 +1,6 @@
 """Headline benchmark: trained images / second of the fairness-finetuning step (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full training step of exp-1-debias-gender/1-main-debias.py:1746-2029 (minus wandb/plots
@@ -10,6 +10,10 @@ Workload = BASELINE.json configs[1]: exp-1-debias-gender, batch 8 per GPU, S=20 
 LoRA rank 4 on the U-Net, fp16, SD-v1.5 512x512, synthetic weights / prompts / noise.
 One process per GPU; weak scaling (each rank trains its own B images, one RCCL all-reduce of the flat
 LoRA-gradient buffer per step).
+
+A plain run sets up, warms up, times K steps, writes the last timed step's outputs (--dump-outputs) and prints the
+result line.  --full adds what takes runs of its own: the roofline step (per-launch HIP events, one stream), the
+reference-schedule A/B steps and the CPU baseline; its whole process is budgeted to finish within 10 minutes.
 """
 import argparse
 import json
@@ -86,12 +90,19 @@ def main():
     ap.add_argument("--force_collectives", action="store_true", help="initialise the process group and run the step's collectives even at world size 1 (RCCL smoke on a one-GPU box)")
     ap.add_argument("--experiment", default="exp-1", choices=["exp-1", "exp-3", "exp-4", "exp-5"], help="exp-3/4/5: multi-attribute head + OT targets (not the headline config)")
     ap.add_argument("--no_regularisers", action="store_true", help="drop the CLIP/DINOv2 image-semantics and SFNet face-realism terms (loss_fair only)")
-    ap.add_argument("--dump_shapes", default=None, help="CSV of the roofline pass's GEMM/conv launches grouped by kernel and shape")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--cpu_baseline_full", action="store_true", help="cfg1-size oracle step (B=2, S=4), warm-up + median of 3 (~15 min)")
-    ap.add_argument("--cpu_baseline_bounded", action="store_true", help="keep the bounded CPU sample (B=1, S=1) even when --steps >= 20")
-    ap.add_argument("--no_roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: the roofline step, the reference-schedule "
+                                                            "A/B steps and the CPU baseline (off by default: a plain run only sets up, warms up and times)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--dump_shapes", default=None, help="--full: CSV of the roofline pass's GEMM/conv launches grouped by kernel and shape")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu_baseline_full", action="store_true", help="--full: cfg1-size oracle step (B=2, S=4), warm-up + median of 3 (~6 min)")
+    ap.add_argument("--cpu_baseline_bounded", action="store_true", help="--full: keep the bounded CPU sample (B=1, S=1) even when --steps >= 20")
+    ap.add_argument("--no_roofline", action="store_true", help="--full: skip the roofline step and the reference-schedule A/B")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    roofline = a.full and not a.no_roofline
 
     os.environ["FD_DTYPE"] = a.dtype          # fixed before the package is imported (selects libfairdiff_hip[_bf16].so)
     import finetune_fair_diffusion_amd  # noqa: F401  (first: its __init__ puts GPU_MAX_HW_QUEUES=8 in the environment, which HIP reads when the device is initialised)
@@ -169,6 +180,8 @@ def main():
         dt = float(t.item())
     ms_per_step = 1e3 * dt / a.steps
     value = world * a.batch * a.steps / dt
+    if a.dump_outputs and rank == 0:      # before anything else runs a step: the arrays are the last timed step's
+        dump_outputs(a.dump_outputs, out, tr.banks)
 
     line = {
         "metric": "training-images/sec (SD-v1.5 512^2, 20-step DPM-Solver++ unroll, fairness-finetune step)",
@@ -214,7 +227,7 @@ def main():
     line["config"].update(r2_steps_prefetched_under_previous_tail=int(tr.last_r2_prefetched), r3_consumes_r1_forward=shared, r1_r2_rollouts_on_two_streams=bool(tr.concurrent_r2), backward_timesteps_on_two_streams=bool(tr.concurrent_bwd), executed_flop_per_image=f_exec,
                           step_mfma_frac_executed=value / world * f_exec / MFMA_PEAK_F16)
 
-    if not a.no_roofline:
+    if roofline:
         # roofline pass: one more identical step with per-launch HIP events on the GEMM/conv kernel family (keyed by the rocprof kernel
         # name) and the per-phase HIP events of the trainer.  EVERY rank runs the step (its collectives must be matched); rank 0 measures.
         if rank == 0:
@@ -223,7 +236,7 @@ def main():
         conc, tr.concurrent_r2, concb, tr.concurrent_bwd = tr.concurrent_r2, False, tr.concurrent_bwd, False     # kernels timed in isolation on one stream
         one_step()
         tr.concurrent_r2, tr.concurrent_bwd = conc, concb
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and roofline:
         summ = ops.TIMER.summary()
         if a.dump_shapes:
             with open(a.dump_shapes, "w") as f:
@@ -264,7 +277,7 @@ def main():
                             "family": {k: {"launches": v["launches"], "ms": round(v["ms"], 2), "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1),
                                            "frac": round(v["flops"] / (v["ms"] * 1e-3) / MFMA_PEAK_F16, 4)}
                                        for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"])}}
-    if world == 1 and not a.no_roofline and shared:
+    if world == 1 and roofline and shared:
         # A/B, informational: the reference's own schedule (R1 and R3 each run their forward rollout; FD_NO_SHARE=1), after the timed region
         tr.share_r1_r3 = False
         one_step()
@@ -283,7 +296,7 @@ def main():
     if a.force_collectives:
         line["config"]["collectives"] = "RCCL process group of world size %d: probability all-gather + flat LoRA-gradient all-reduce executed" % world
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.tiny:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not a.tiny:
         del tr, models
         torch.cuda.empty_cache()
         # the section-8(d) protocol (cfg1: B=2, S=4, warm-up + median of 3, ~8 min on 16 threads) whenever the run is long enough to be the driver's
@@ -307,9 +320,56 @@ def cpu_model():
 
 
 T_START = time.perf_counter()
-# wall-clock budget of the whole bench.py process (the driver's limit is 1800 s): the cfg1 CPU protocol drops from median-of-3 to fewer timed
-# steps (and says so) when its warm-up step shows that three would not fit
-BUDGET_S = float(os.environ.get("FD_BENCH_BUDGET_S", "1200"))
+# wall-clock budget of the whole bench.py --full process (which must end within 10 minutes): the cfg1 CPU protocol drops from median-of-3 to
+# fewer timed steps (and says so) when its warm-up step shows that three would not fit
+BUDGET_S = float(os.environ.get("FD_BENCH_BUDGET_S", "540"))
+
+DUMP_BYTES = 60 * 2 ** 20     # --dump-outputs: at most this many bytes of array data in all
+DUMP_WHOLE = 1 << 18          # arrays up to this many elements are written whole; larger ones share the rest of the budget as samples
+
+
+def dump_outputs(path, out, banks):
+    """--dump-outputs: every array the last timed step handed its caller (``train_step``'s dict; nested dicts as ``<key>.<sub>``, numbers as
+    0-d arrays) plus what it left in the trainable state (``lora<i>_weights`` after the update, ``lora<i>_grad``), as ``path/<name>.npy``.
+    Floating point is written as float32 (float64 stays float64), integers and flags as float64.  An array larger than DUMP_WHOLE elements
+    is written as a fixed sample: the elements of its flattened form at sorted indices drawn without replacement by numpy's default_rng(0),
+    the same for every run of the same arguments, so that two builds can be compared output for output."""
+    import re
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def add(name, v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                add("%s.%s" % (name, k), v[k])
+        elif isinstance(v, torch.Tensor):
+            arrays[re.sub(r"[^A-Za-z0-9_.-]", "_", name)] = v.detach()
+        elif isinstance(v, (bool, int, float)):
+            arrays[re.sub(r"[^A-Za-z0-9_.-]", "_", name)] = torch.tensor(float(v), dtype=torch.float64)
+
+    for k in sorted(out):
+        add(k, out[k])
+    for i, bank in enumerate(banks):
+        add("lora%d_weights" % i, bank.flat)
+        add("lora%d_grad" % i, bank.grad)
+    if any(v.is_cuda for v in arrays.values()):
+        torch.cuda.synchronize()
+
+    def npdtype(v):
+        return np.float32 if v.is_floating_point() and v.dtype != torch.float64 else np.float64
+
+    big = [n for n, v in arrays.items() if v.numel() > DUMP_WHOLE]
+    small_bytes = sum(v.numel() * np.dtype(npdtype(v)).itemsize for n, v in arrays.items() if n not in big)
+    share = (DUMP_BYTES - small_bytes) // len(big) if big else 0          # bytes per sampled array
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        dt = npdtype(v)
+        cap = max(1, share // np.dtype(dt).itemsize)
+        if name in big and v.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), size=cap, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(path, name + ".npy"), v.cpu().to(torch.float64).numpy().astype(dt))
 
 
 def cpu_baseline(S, full=False, t_start=None):
