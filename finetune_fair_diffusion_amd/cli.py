@@ -7,16 +7,17 @@ cannot be set from YAML and booleans follow Python's ``bool(value)`` -- plus the
   --num_denoising_steps  fixed S instead of ``random.choices(range(19,24))`` (:1779)
   --synthetic            synthetic weights / token ids / face provider (no network, no data.zip)
   --face_provider        detector seam: "synthetic" (default) or "detector" (insightface + face_recognition, when installed)
-  --num_classifier_logits  80 (exp-1) / 6 (exp-3,5) / 8 (exp-4)
+  --num_classifier_logits  80 (exp-1) / 6 (exp-3,5,6) / 8 (exp-4)
   --lora_up_std          std of the LoRA ``up`` init; 0 (default) = zeros like the reference, non-zero only for synthetic experiments
 
 The multi-attribute experiments change a few flags and defaults (exp-3-debias-gender-race/1-main-debias.py:343-660,
 exp-4-debias-gender-race-age/...:343-672, exp-5-...:343-690; exp-2-debias-gender-token/...:453-780 drops the two LoRA switches and adds
 ``--train_num_tokens``): ``factor{1,2}`` split per attribute,
-``face_gender[_race[_age]]_confidence_level``, bigger batches, three more prompt files in exp-5 -- ``EXPERIMENT_CLI``.
+``face_gender[_race[_age]]_confidence_level``, bigger batches, three more prompt files in exp-5 -- ``EXPERIMENT_CLI``.  exp-6
+(exp-6-debias-race/1-main-debias.py:337-644) keeps exp-1's flags with other defaults and ``face_race_confidence_level``.
 
-Pinned by tests/golden/reference_cli.json and reference_cli_multi.json (defaults and every YAML overlay of
-exp-1/2/3/4/5, produced by running the reference's own parse_args).
+Pinned by tests/golden/reference_cli.json, reference_cli_multi.json and reference_cli_exp6.json (defaults and every YAML overlay of
+exp-1/2/3/4/5/6, produced by running the reference's own parse_args).
 """
 import argparse
 import os
@@ -43,6 +44,11 @@ EXPERIMENT_CLI = {
               dict(prompt_occupation_w_style_and_context_path="../data/1-prompts/occupation_w_style_and_context.json",
                    prompt_personal_descroptor_path="../data/1-prompts/personal_descriptor.json",   # (sic) the reference's spelling
                    prompt_sports_path="../data/1-prompts/sports.json")),
+    # exp-6 (race alone, exp-6-debias-race/1-main-debias.py:337-644): exp-1's flags on the GenderRace4 classifier, race confidence level
+    "exp-6": (dict(max_train_steps=12000, weight_loss_img=6, weight_loss_face=0.1, factor1=0.6, factor2=0.3, train_images_per_prompt_GPU=16,
+                   val_images_per_prompt_GPU=16, classifier_weight_path=_FF + "GenderRace4_09041216/epoch=9-step=3380_MobileNetLarge.pt",
+                   face_feats_path=_MULTI["face_feats_path"]),
+              ["face_gender_confidence_level"], dict(face_race_confidence_level=0.9), {}),
 }
 
 

@@ -10,6 +10,9 @@
 // draws are independent workgroups; a face's seat is added into the summed plan with a float atomic (integer-valued sums <= S: exact
 // and order-independent).  Latency-bound by design (S = 100 waves on 256 CUs, ~N^2 dependent steps each): it exists to take the solve
 // off the host, not to fill the chip.
+//
+// exp-6 (``fd_ot_expected_targets``) runs the same solver once per kept composition of N faces into the four race classes, without a plan
+// (seats only), and reduces the seats to the weighted expected plan, its argmax and 1 - max on the device.
 #include "common.h"
 
 namespace {
@@ -123,9 +126,66 @@ __global__ __launch_bounds__(64) void ot_assign_kernel(const double* __restrict_
     }
     for (int j = lane + 1; j <= N; j += 64) {
         const int row = p[j] - 1;
-        atomicAdd(plan + (size_t)row * K + cell[j], 1.0f);
+        if (plan) atomicAdd(plan + (size_t)row * K + cell[j], 1.0f);
         if (seats) seats[(size_t)blockIdx.x * N + row] = cell[j];
     }
+}
+
+// IEEE round-to-nearest x / y.  The library builds with -ffast-math, under which ``x / y`` becomes a reciprocal-and-refine sequence that can
+// differ from the host in the last bit; this is the sequence the compiler emits for an exact fp64 division (scale, reciprocal, two Newton
+// steps, remainder, fmas, fixup), written with the intrinsics so that no fast-math rewrite applies.
+__device__ __forceinline__ double div_rn(double x, double y) {
+    bool unused;
+    const double ds = __builtin_amdgcn_div_scale(x, y, false, &unused);      // scaled denominator
+    const double r0 = __builtin_amdgcn_rcp(ds);
+    const double e0 = __builtin_fma(-ds, r0, 1.0);
+    const double r1 = __builtin_fma(r0, e0, r0);
+    const double e1 = __builtin_fma(-ds, r1, 1.0);
+    bool scaled;
+    const double ns = __builtin_amdgcn_div_scale(x, y, true, &scaled);       // scaled numerator
+    const double r2 = __builtin_fma(r1, e1, r1);
+    const double q = ns * r2;
+    const double rem = __builtin_fma(-ds, q, ns);
+    return __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(rem, r2, q, scaled), y, x);
+}
+
+// exp-6's expected transport plan (exp-6-debias-race/1-main-debias.py:1414-1483): ``target_probs += T_s * w_s`` over the kept compositions s in
+// table order, row L1 normalisation, first argmax, 1 - max.  One thread per face with its K <= 16 fp64 cell sums in registers; the seats of
+// composition s are read as one coalesced row of [S, N].  T_s is 0/1, so ``if (seat == k) acc[k] += w_s`` is the host's ``T * w`` sum bit for
+// bit; the row sum is sequential over the cells like numpy's 4-wide ``norm(ord=1)``.  No atomics: the result does not depend on scheduling.
+__global__ __launch_bounds__(1024) void ot_weighted_targets_kernel(const int* __restrict__ seats, const double* __restrict__ weights, int* targets,
+                                                                   double* uncertainty, int N, int K, int S) {
+#pragma clang fp reassociate(off) contract(off)     // the library builds with -ffast-math: keep the host's operation order
+    const int i = threadIdx.x;
+    if (i >= N) return;
+    double acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const int seat = seats[(size_t)s * N + i];
+        const double w = weights[s];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (seat == k) acc[k] += w;
+    }
+    double l1 = acc[0];
+#pragma unroll
+    for (int k = 1; k < 16; ++k)
+        if (k < K) l1 += acc[k];
+    int best = 0;
+    double pmax = div_rn(acc[0], l1);
+#pragma unroll
+    for (int k = 1; k < 16; ++k) {
+        if (k < K) {
+            const double pk = div_rn(acc[k], l1);
+            if (pk > pmax) {      // strict: the first maximal cell, like argmax
+                pmax = pk;
+                best = k;
+            }
+        }
+    }
+    targets[i] = best;
+    uncertainty[i] = 1.0 - pmax;
 }
 
 }  // namespace
@@ -135,4 +195,17 @@ extern "C" int fd_ot_assign_sum(const double* cost, const int32_t* counts, float
     const size_t lds = (size_t)(N + 1) * (3 * sizeof(double) + 4 * sizeof(int));
     hipLaunchKernelGGL(ot_assign_kernel, dim3(S), dim3(64), lds, (hipStream_t)stream, cost, (const int*)counts, plan, (int*)seats, N, K);
     return fd_check_launch("fd_ot_assign_sum");
+}
+
+extern "C" int fd_ot_expected_targets(const double* cost, const int32_t* counts, const double* weights, int32_t* seats, int32_t* targets,
+                                      double* uncertainty, int N, int K, int S, void* stream) {
+    FD_REQUIRE(N >= 1 && N <= 1024 && K >= 1 && K <= 16 && S >= 1, "fd_ot_expected_targets: N=%d (1..1024) K=%d (1..16) S=%d (>= 1)", N, K, S);
+    FD_REQUIRE(cost && counts && weights && seats && targets && uncertainty, "fd_ot_expected_targets: null buffer");
+    const size_t lds = (size_t)(N + 1) * (3 * sizeof(double) + 4 * sizeof(int));
+    hipLaunchKernelGGL(ot_assign_kernel, dim3(S), dim3(64), lds, (hipStream_t)stream, cost, (const int*)counts, (float*)nullptr, (int*)seats, N, K);
+    const int rc = fd_check_launch("fd_ot_expected_targets (assignment)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ot_weighted_targets_kernel, dim3(1), dim3((N + 63) / 64 * 64), 0, (hipStream_t)stream, (const int*)seats, weights, (int*)targets,
+                       uncertainty, N, K, S);
+    return fd_check_launch("fd_ot_expected_targets (reduction)");
 }

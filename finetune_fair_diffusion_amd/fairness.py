@@ -297,6 +297,24 @@ def _cells(attr_sizes):
     return list(it.product(*[range(k) for k in attr_sizes]))
 
 
+def _corner_cost(P, sizes, age_asymmetric=False):
+    """Cost matrix [N, K] fp64: euclidean distance of the probability vectors (per attribute an fp32 array [N, k_a]) to the one-hot corners
+    of each cell (exp-3 `:1514-1531`; exp-6 `:1461` -- POT's ``ot.dist(metric="euclidean")``, whose ``p`` is ignored)."""
+    N = P[0].shape[0]
+    cells = _cells(sizes)
+    M = np.zeros((N, len(cells)))
+    for j, cell in enumerate(cells):
+        sq = np.zeros(N)
+        for a, c in enumerate(cell):
+            onehot = np.zeros(sizes[a]); onehot[c] = 1.0
+            d = P[a] - onehot
+            if age_asymmetric and a == len(sizes) - 1 and c == 1:
+                d = d.copy(); d[:, 0] *= 2.0
+            sq += (d ** 2).sum(axis=1)
+        M[:, j] = np.sqrt(sq)
+    return M
+
+
 @torch.no_grad()
 def mc_transport_problem(probs_list, class_cdfs, num_samples_per_device=100, generator=None, age_asymmetric=False):
     """The inputs of the Monte-Carlo transport solves (exp-3 `:1488-1536`, exp-4 `:1517-1569`): returns (idx [n] bool of faces, cost
@@ -325,17 +343,7 @@ def mc_transport_problem(probs_list, class_cdfs, num_samples_per_device=100, gen
             lo = hi
         draws.append(cls.numpy())
     radix = np.array([int(np.prod(sizes[a + 1:])) for a in range(len(sizes))])
-    # cost matrix: distance of the probability vectors to the one-hot corners of each cell (`:1514-1531`)
-    M = np.zeros((N, K))
-    for j, cell in enumerate(cells):
-        sq = np.zeros(N)
-        for a, c in enumerate(cell):
-            onehot = np.zeros(sizes[a]); onehot[c] = 1.0
-            d = P[a] - onehot
-            if age_asymmetric and a == len(sizes) - 1 and c == 1:
-                d = d.copy(); d[:, 0] *= 2.0
-            sq += (d ** 2).sum(axis=1)
-        M[:, j] = np.sqrt(sq)
+    M = _corner_cost(P, sizes, age_asymmetric)
     counts = np.zeros((num_samples_per_device, K), dtype=np.int64)
     for s in range(num_samples_per_device):
         cell_idx = sum(draws[a][s] * radix[a] for a in range(len(sizes)))
@@ -407,6 +415,89 @@ def generate_dynamic_targets_multi(probs_list, class_cdfs, num_samples_per_devic
     return res
 
 
+# ------------------------------------------------------------------------------------------ exp-6 (race, exact enumeration)
+_COMPOSITION_TABLES = {}
+TABLE_MASS = 0.95
+
+
+def composition_table(N, K=4):
+    """The compositions of N faces into K = 4 race classes that exp-6 transports onto (exp-6-debias-race/1-main-debias.py:1439-1454), cached
+    per N: ``(counts [S, 4] int32, weights [S] float64)`` in kept order.
+
+    Every composition (n1, .., n4) -- enumerated with n1 outermost -- carries its multinomial coefficient (exact Python ints; numpy makes an
+    int64 array up to N = 35 and an object array from 36 on, where the coefficients overflow int64), normalised by ``np.linalg.norm(ord=1)``.
+    The weights are sorted descending and kept until their sequential running sum exceeds 0.95 (strict).  The sort is
+    ``np.flip(np.argsort(w, kind="stable"))``: the reference's expression with a stable sort, so that the kept set does not depend on the CPU
+    (numpy's default float sort is SIMD-dispatched and orders the equal-weight compositions at the cutoff differently on different machines;
+    only the membership of that cutoff tie group can differ from a given reference run).  N = 0: an empty table."""
+    assert K == 4
+    tab = _COMPOSITION_TABLES.get(N)
+    if tab is not None:
+        return tab
+    if N == 0:
+        tab = (np.zeros((0, K), dtype=np.int32), np.zeros(0, dtype=np.float64))
+    else:
+        combs, coefs = [], []
+        for n1 in range(N + 1):
+            for n2 in range(N - n1 + 1):
+                for n3 in range(N - n1 - n2 + 1):
+                    combs.append((n1, n2, n3, N - n1 - n2 - n3))
+                    coefs.append(math.comb(N, n1) * math.comb(N - n1, n2) * math.comb(N - n1 - n2, n3))
+        w = np.array(coefs)
+        w = w / np.linalg.norm(w, ord=1)
+        order = np.flip(np.argsort(w, kind="stable"))
+        mass = 0.0
+        for last, j in enumerate(order):
+            mass += w[j]
+            if mass > TABLE_MASS:
+                break
+        keep = order[:last + 1]
+        tab = (np.array(combs, dtype=np.int32)[keep], np.asarray(w[keep], dtype=np.float64))
+    _COMPOSITION_TABLES[N] = tab
+    return tab
+
+
+@torch.no_grad()
+def expected_transport_targets(probs, device=None, table=None):
+    """exp-6's dynamic targets (``generate_dynamic_targets_race``, exp-6-debias-race/1-main-debias.py:1414-1483) for the gathered race
+    probabilities ``probs`` [n, 4] (-1 rows = no face): for every kept composition of the N faces (``composition_table``) the exact transport
+    ``ot.emd(ones(N), counts_s, M)`` onto the one-hot corners, the plans summed with the composition weights (sequentially, in table order,
+    fp64), each row normalised by its L1 norm (``((t0+t1)+t2)+t3``), the first argmax as the target and 1 - max as the uncertainty.
+    Returns (targets [n] long, uncertainty [n] float64), -1 where there is no face (every entry without faces).
+
+    ``device``: solve and reduce on that GPU (``fd_ot_expected_targets``: one wave per composition, then one thread per face -- bit-equal to the
+    host statement wherever the optimal plans are unique); None: scipy's assignment per composition.  ``table``: (counts, weights) to use instead
+    of the cached one (tests inject a recorded reference table)."""
+    probs = probs.detach().cpu()
+    n = probs.shape[0]
+    idx = (probs != -1).all(dim=-1)
+    t_all = torch.full([n], -1, dtype=torch.long)
+    u_all = torch.full([n], -1.0, dtype=torch.float64)
+    N = int(idx.sum())
+    if N == 0:
+        return t_all, u_all
+    M = _corner_cost([probs[idx].float().numpy()], [probs.shape[1]])
+    counts, weights = composition_table(N, probs.shape[1]) if table is None else table
+    counts = np.asarray(counts, dtype=np.int32)
+    weights = np.asarray(weights, dtype=np.float64)
+    if device is not None:
+        from . import ops
+        t, u = ops.ot_expected_targets(torch.from_numpy(M).to(device), torch.from_numpy(counts).to(device), torch.from_numpy(weights).to(device))
+        t_all[idx] = t.cpu().long()           # read back on the caller's current stream
+        u_all[idx] = u.cpu()
+        return t_all, u_all
+    acc = np.zeros(M.shape)
+    for s in range(counts.shape[0]):
+        acc += _ot_assign(M, counts[s]) * weights[s]
+    l1 = acc[:, 0].copy()
+    for k in range(1, acc.shape[1]):
+        l1 += acc[:, k]
+    tp = acc / l1[:, None]
+    t_all[idx] = torch.from_numpy(tp.argmax(axis=-1)).long()
+    u_all[idx] = torch.from_numpy(1 - tp.max(axis=-1))
+    return t_all, u_all
+
+
 # per experiment: (factor1 flags, factor2 flags, confidence-level flag) of the regulariser terms, in attribute order
 EXPERIMENT_REG_FLAGS = {
     "exp-1": (["factor1"], ["factor2"], "face_gender_confidence_level"),
@@ -414,6 +505,7 @@ EXPERIMENT_REG_FLAGS = {
     "exp-3": (["factor1_gender", "factor1_race"], ["factor2_gender", "factor2_race"], "face_gender_race_confidence_level"),
     "exp-4": (["factor1_gender", "factor1_race", "factor1_age"], ["factor2_gender", "factor2_race", "factor2_age"], "face_gender_race_age_confidence_level"),
     "exp-5": (["factor1_gender", "factor1_race"], ["factor2_gender", "factor2_race"], "face_gender_race_confidence_level"),
+    "exp-6": (["factor1"], ["factor2"], "face_race_confidence_level"),
 }
 
 EXPERIMENT_ATTRS = {
@@ -423,4 +515,5 @@ EXPERIMENT_ATTRS = {
     "exp-3": (6, [("gender", 0, 2), ("race", 2, 4)], [[0.5, 1.0], [0.25, 0.5, 0.75, 1.0]], False),
     "exp-4": (8, [("gender", 0, 2), ("race", 2, 4), ("age", 6, 2)], [[0.5, 1.0], [0.25, 0.5, 0.75, 1.0], [0.75, 1.0]], True),
     "exp-5": (6, [("gender", 0, 2), ("race", 2, 4)], [[0.5, 1.0], [0.25, 0.5, 0.75, 1.0]], False),
+    "exp-6": (6, [("race", 2, 4)], None, False),      # race alone on the GenderRace4 head: exact-enumeration targets (expected_transport_targets)
 }

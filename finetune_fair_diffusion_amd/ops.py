@@ -776,6 +776,21 @@ def ot_assign_sum(cost, counts, plan=None, seats=False):
     return (plan, st) if seats else plan
 
 
+def ot_expected_targets(cost, counts, weights, return_seats=False):
+    """exp-6's dynamic targets (exp-6 :1414-1483) on the device: cost [N,K] f64, counts [S,K] int32 (the kept compositions in table order, rows
+    sum to N), weights [S] f64.  Returns targets [N] int32 (first argmax of the L1-normalised expected plan) and uncertainty [N] f64 (1 - max),
+    plus the per-composition seats [S,N] int32 with ``return_seats``."""
+    N, K = cost.shape
+    S = counts.shape[0]
+    assert counts.shape[1] == K and weights.shape == (S,)
+    st = torch.empty((S, N), dtype=torch.int32, device=cost.device)
+    t = torch.empty((N,), dtype=torch.int32, device=cost.device)
+    u = torch.empty((N,), dtype=torch.float64, device=cost.device)
+    _call("fd_ot_expected_targets", _p(_chk(cost, torch.float64)), _p(_chk(counts, torch.int32)), _p(_chk(weights, torch.float64)), _p(st), _p(t), _p(u),
+          N, K, S, _stream())
+    return (t, u, st) if return_seats else (t, u)
+
+
 # ----------------------------------------------------------------------------- text-encoder attention
 def small_attn_fwd(q, k, v, key_valid, B, H, T, d, scale, causal=True, save_p=False):
     o = torch.empty_like(q)

@@ -32,8 +32,8 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import ops
-from .fairness import (EXPERIMENT_ATTRS, EXPERIMENT_REG_FLAGS, SyntheticFaceProvider, face_grad_factors, face_grad_factors_multi,
-                       fair_loss_and_grad, gen_dynamic_weights, gen_dynamic_weights_multi,
+from .fairness import (EXPERIMENT_ATTRS, EXPERIMENT_REG_FLAGS, SyntheticFaceProvider, composition_table, expected_transport_targets,
+                       face_grad_factors, face_grad_factors_multi, fair_loss_and_grad, gen_dynamic_weights, gen_dynamic_weights_multi,
                        generate_dynamic_targets, mc_transport_plan, microbatch_weights, targets_from_plan)
 from . import fairness_dev as FD
 from . import unet as unet_mod
@@ -187,8 +187,10 @@ class FairnessTrainer:
         _, self.attrs, self.class_cdfs, self.age_asym = EXPERIMENT_ATTRS[experiment]
         # exp-1 (one binary attribute): probabilities, dynamic targets, loss, dynamic weights and hook factors stay ON THE DEVICE (fairness_dev.py);
         # what the caller is told about the step (probabilities, targets, per-image losses) comes back in ONE read-back together with the
-        # finite flag.  The multi-attribute experiments keep the host path (their OT solve has its own worker thread / device solver).
-        self.device_tail = len(self.attrs) == 1 and self.attrs[0][2] == 2 and not _HOST_TAIL
+        # finite flag.  The multi-attribute experiments and exp-6 keep the host path (their OT solve has its own worker thread / device solver).
+        self.device_tail = experiment in ("exp-1", "exp-2") and len(self.attrs) == 1 and self.attrs[0][2] == 2 and not _HOST_TAIL
+        # exp-6: one 4-class attribute whose targets are the expected transport plan over the exact enumeration of class compositions
+        self.enumerated_targets = experiment == "exp-6"
         self._binom = {}
         self._pending_readback = None
         self.target_rng = torch.Generator().manual_seed(1234 + rank)
@@ -268,6 +270,8 @@ class FairnessTrainer:
         self.ot_on_device = os.environ.get("FD_OT_HOST") is None
         self._ot_stream = torch.cuda.Stream(device=self.device)
         self._tgt = None
+        if self.enumerated_targets:      # the table of the usual global face count (every image has a face); other counts are built on the worker
+            composition_table(world_size * getattr(args, "train_images_per_prompt_GPU", 0))
 
     # ------------------------------------------------------------------ per-phase timing (R1 / R2 / R3-fwd / R3-bwd / sync)
     def _mark(self, name):
@@ -552,7 +556,10 @@ class FairnessTrainer:
           * exp-1: the binomial-rank targets, inline (microseconds);
           * exp-3/4/5: the 100 Monte-Carlo transport solves of this rank start on a WORKER THREAD -- they only need the gathered
             probabilities, and nothing needs the targets before R3's loss, so they run underneath the R2 rollout that the main thread
-            keeps enqueueing (the reference solves them serially between R1 and R2 on every rank, exp-3 `:1488-1536`)."""
+            keeps enqueueing (the reference solves them serially between R1 and R2 on every rank, exp-3 `:1488-1536`);
+          * exp-6: the same worker thread solves one transport problem per kept composition of the global faces and reduces them to the
+            expected plan's targets (``fd_ot_expected_targets``, exp-6 `:1414-1483`); every rank computes the whole result from the same
+            gathered probabilities, as the reference does, so there is nothing to all-reduce."""
         if getattr(self, "device_tail", False) and per[0]["probs"].is_cuda:
             pd = per[0]["probs"]
             if self.collectives:
@@ -570,8 +577,9 @@ class FairnessTrainer:
             for _, _, k in self.attrs:
                 gathered.append(allp[:, c:c + k].contiguous())
                 c += k
-        self._tgt = dict(B=B, single=len(per) == 1)
-        if len(per) == 1:
+        enumerated = getattr(self, "enumerated_targets", False)
+        self._tgt = dict(B=B, single=len(per) == 1 and not enumerated)
+        if self._tgt["single"]:
             self._tgt["res"] = [generate_dynamic_targets(gathered[0], w_uncertainty=True)]
             return
 
@@ -580,7 +588,15 @@ class FairnessTrainer:
         def work():
             t0 = time.perf_counter()
             try:
-                if self.ot_on_device:       # fd_ot_assign_sum on a side stream of this thread; the summed plan stays in HBM for the all-reduce
+                if enumerated:
+                    if self.ot_on_device:       # inputs up, solves, reduction and the read-back all on the side stream of this thread
+                        with torch.cuda.stream(self._ot_stream):
+                            t, u = expected_transport_targets(gathered[0], device=self.device)
+                        self._ot_stream.synchronize()
+                    else:
+                        t, u = expected_transport_targets(gathered[0])
+                    st["res"] = [(t, u.float())]
+                elif self.ot_on_device:       # fd_ot_assign_sum on a side stream of this thread; the summed plan stays in HBM for the all-reduce
                     with torch.cuda.stream(self._ot_stream):
                         idx, tp, sizes = mc_transport_plan(gathered, self.class_cdfs, 100, self.target_rng, self.age_asym, device=self.device)
                         if tp is not None and not self.collectives:
@@ -617,16 +633,17 @@ class FairnessTrainer:
                 failed = f.cpu()
             if float(failed) != 0:
                 self._tgt = None
-                raise RuntimeError("Monte-Carlo transport solve for the dynamic targets failed" +
+                raise RuntimeError("transport solve for the dynamic targets failed" +
                                    (" on this rank" if "error" in st else " on another rank")) from st.get("error")
-            idx, tp, sizes = st["plan"]
-            if tp is not None and tp.is_cuda:
-                tp.record_stream(torch.cuda.current_stream())
-            if tp is not None and self.collectives:
-                t = tp.to(self.device)
-                dist.all_reduce(t, op=dist.ReduceOp.SUM)
-                tp = t
-            st["res"] = targets_from_plan(idx, tp, sizes)
+            if "res" not in st:             # exp-3/4/5: the summed plans of all ranks (exp-6's worker already produced the targets)
+                idx, tp, sizes = st["plan"]
+                if tp is not None and tp.is_cuda:
+                    tp.record_stream(torch.cuda.current_stream())
+                if tp is not None and self.collectives:
+                    t = tp.to(self.device)
+                    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                    tp = t
+                st["res"] = targets_from_plan(idx, tp, sizes)
             self.last_ot_ms = (st.get("solve_ms", 0.0), 1e3 * (time.perf_counter() - t0))
         out = []
         for t, u in st["res"]:

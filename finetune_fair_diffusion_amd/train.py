@@ -1,6 +1,6 @@
 """Training driver: the loop of exp-1-debias-gender/1-main-debias.py ``main`` (:647-2070) around FairnessTrainer.
 
-    python -m finetune_fair_diffusion_amd.train [--experiment exp-1|exp-2|exp-3|exp-4|exp-5] --config <yaml> [--synthetic]
+    python -m finetune_fair_diffusion_amd.train [--experiment exp-1|exp-2|exp-3|exp-4|exp-5|exp-6] --config <yaml> [--synthetic]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m finetune_fair_diffusion_amd.train ...
 
 Same flags, YAML overlay, seeding (``set_seed(seed, device_specific=True)`` :693, prompt order from
@@ -98,7 +98,7 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
     if experiment is None:       # build addition: one driver for the reference's per-experiment scripts
         import argparse
         pre = argparse.ArgumentParser(add_help=False)
-        pre.add_argument("--experiment", default="exp-1", choices=["exp-1", "exp-2", "exp-3", "exp-4", "exp-5"])
+        pre.add_argument("--experiment", default="exp-1", choices=["exp-1", "exp-2", "exp-3", "exp-4", "exp-5", "exp-6"])
         ns, argv = pre.parse_known_args(argv)
         experiment = ns.experiment
     args = parse_args(argv, with_extras=True, experiment=experiment)

@@ -327,6 +327,13 @@ int fd_rect_scale(float* dimg, const int32_t* rects, const float* factors, int B
  * wave per draw.  cost [N,K] f64, counts [S,K] int32, plan [N,K] f32: plan += sum_s T_s (0/1 transport matrices; zero it first for a
  * fresh sum); seats [S,N] int32 (cell of face i in draw s) or NULL.  N <= 1024. */
 int fd_ot_assign_sum(const double* cost, const int32_t* counts, float* plan, int32_t* seats, int N, int K, int S, void* stream);
+/* ---- dynamic targets of exp-6 (exp-6-debias-race/1-main-debias.py:1414-1483): the expected transport plan over the kept compositions of the N
+ * faces into K cells.  For every composition s the exact assignment above runs with seats only (no plan); then, per face, the cell sums
+ * acc[k] = sum_s w_s [seat_s == k] in table order (fp64), the row L1 normalisation, the first argmax (targets [N] int32) and 1 - max
+ * (uncertainty [N] f64).  cost [N,K] f64, counts [S,K] int32 (rows sum to N), weights [S] f64, seats [S,N] int32 workspace (holds every
+ * composition's seats on return).  N 1..1024, K 1..16, S >= 1; both kernels run on ``stream``. */
+int fd_ot_expected_targets(const double* cost, const int32_t* counts, const double* weights, int32_t* seats, int32_t* targets, double* uncertainty,
+                           int N, int K, int S, void* stream);
 
 #ifdef __cplusplus
 }
