@@ -124,8 +124,15 @@ __global__ void add_kernel(const f16* a, const f16* b, f16* y, int64_t n, float 
         y[i] = (f16)(sa * (float)a[i] + (b ? sb * (float)b[i] : 0.f));
     }
 }
+// y = fp16(fp32(x * scale)): one fp32 multiply, one round-to-nearest-even conversion, the sign of zero kept (torch's (x * scale).half(), bit for bit).
+// Under the library's -ffast-math (no signed zeros) the compiler fused multiply and conversion into v_fma_mix with a +0 addend, which turned
+// -0 into +0 (and rounded the exact product once instead of the fp32 product); the empty asm keeps the fp32 product as the value converted.
 __global__ void cast_f32_f16_kernel(const float* x, f16* y, int64_t n, float scale) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = (f16)(x[i] * scale);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float v = x[i] * scale;
+        asm volatile("" : "+v"(v));
+        y[i] = (f16)v;
+    }
 }
 __global__ void cast_f16_f32_kernel(const f16* x, float* y, int64_t n, float scale) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = (float)x[i] * scale;

@@ -1,6 +1,7 @@
 """Kernel-level parity (GPU): every HIP kernel vs a plain fp32 PyTorch statement of the same op,
 called through the C-ABI (ops.py -> libfairdiff_hip.so).  Tolerances are fp16-output tolerances:
-|err| <= tol * max|ref| with tol stated per test."""
+|err| <= tol * max|ref| with tol stated per test.  Production shapes and edges of the smaller entry points are in
+test_kernels_edges_gpu.py; tests/test_kernel_coverage_cpu.py fails when an entry point has no direct test in either."""
 import math
 
 import pytest
