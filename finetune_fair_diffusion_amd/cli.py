@@ -9,6 +9,8 @@ cannot be set from YAML and booleans follow Python's ``bool(value)`` -- plus the
   --face_provider        detector seam: "synthetic" (default) or "detector" (insightface + face_recognition, when installed)
   --num_classifier_logits  80 (exp-1) / 6 (exp-3,5,6) / 8 (exp-4)
   --lora_up_std          std of the LoRA ``up`` init; 0 (default) = zeros like the reference, non-zero only for synthetic experiments
+  --validation           off (default) / metrics / grids: the reference's ``evaluation_step`` at step 0 and every ``--evaluate_every_n_iter`` steps
+                         (evaluation.py); "off" leaves the run -- JSON lines, random streams, checkpoints -- exactly as without the flag
 
 The multi-attribute experiments change a few flags and defaults (exp-3-debias-gender-race/1-main-debias.py:343-660,
 exp-4-debias-gender-race-age/...:343-672, exp-5-...:343-690; exp-2-debias-gender-token/...:453-780 drops the two LoRA switches and adds
@@ -127,7 +129,7 @@ def build_parser(experiment="exp-1"):
     return p
 
 
-EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="synthetic", num_classifier_logits=80, lora_up_std=0.0)
+EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="synthetic", num_classifier_logits=80, lora_up_std=0.0, validation="off")
 
 
 def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
@@ -138,6 +140,7 @@ def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
         p.add_argument("--face_provider", type=str, default="synthetic")
         p.add_argument("--num_classifier_logits", type=int, default=80)
         p.add_argument("--lora_up_std", type=float, default=0.0)
+        p.add_argument("--validation", type=str, default="off", choices=["off", "metrics", "grids"])
     args = p.parse_args(input_args) if input_args is not None else p.parse_args()
     if args.config:
         with open(args.config, "r") as f:

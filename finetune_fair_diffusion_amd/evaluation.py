@@ -1,0 +1,325 @@
+"""In-training validation: ``evaluate_process`` / ``evaluation_step`` of exp-1-debias-gender/1-main-debias.py (:1449-1571, :1659-1690) and
+the ``get_evaluate_metrics`` variants of the other experiments (exp-3/5 :1716-1749, exp-4 :1780-1821, exp-6 :1624-1637) on FairnessTrainer.
+
+Per validation prompt the frozen pair and then the evaluated pair generate ``val_images_per_prompt_GPU`` images with 25 denoising steps;
+the classifier's probability table stays on the device, where ONE launch (``ops.eval_tally``, csrc/evaluate.hip) reduces it to integer
+counts and, with ``--validation grids``, one launch (``ops.eval_grid``) paints the whole annotated grid of ``plot_in_grid`` (:151-217) as
+uint8 -- the host reads back 32 integers and the finished grid instead of N x 3 x 512 x 512 images and probability tables.
+``gap_metrics`` turns the counts into the reference's floats with the reference's fp32 operations; ``tally_host`` / ``grid_host`` are the
+plain host statements both kernels are tested against.
+
+The EMA pass rewrites the 16-bit LoRA operand copies from ``bank.ema`` (``refresh_lora(ema=True)``) and back from ``bank.flat`` afterwards:
+no fp32 parameter, EMA or optimiser buffer is copied or written.
+"""
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+N_DENOISING_STEPS_VAL = 25           # :1453
+MAX_ATTR, MAX_K = 3, 4
+# layout of the int32 counts ``fd_eval_tally`` writes (include/fairdiff_hip.h): per attribute a, at 6*a: n_valid, hist[0..3], n(max < 0.8)
+ATTR_STRIDE, OFF_HIST, OFF_BELOW = 6, 1, 5
+OFF_P1_HI, OFF_P1_LO, OFF_P1_MID, OFF_JOINT, OFF_JOINT_VALID, N_COUNTS = 18, 19, 20, 21, 29, 32
+STRIP, FRAME, BOX_WIDTH = 50, 10, 4
+
+# class colour of the first attribute, index = pred + 1 (pred -1 = no face): the reference's PIL colour names as RGB
+PALETTE_GENDER = [(255, 255, 255), (255, 0, 0), (0, 0, 255)]                                   # white / red / blue (exp-1 :179-187)
+PALETTE_RACE = [(255, 255, 255), (50, 205, 50), (0, 0, 0), (165, 42, 42), (255, 165, 0)]       # white / limegreen / black / brown / orange (exp-6 :188-197)
+
+
+def table_attrs(trainer_attrs):
+    """[(column offset, k)] of the attributes inside the concatenated [N, sum k] probability table."""
+    out, c = [], 0
+    for _, _, k in trainer_attrs:
+        out.append((c, k))
+        c += k
+    return out
+
+
+def tally_host(probs, attrs):
+    """The plain torch statement of ``fd_eval_tally``: probs [N, >= sum k] fp32 on the CPU (-1 rows = no face), attrs [(c0, k)] -> int32 [32]."""
+    probs = probs.detach().to("cpu", torch.float32)
+    assert 1 <= len(attrs) <= MAX_ATTR and all(1 <= k <= MAX_K for _, k in attrs)
+    counts = torch.zeros(N_COUNTS, dtype=torch.int32)
+    valid, preds = [], []
+    for a, (c0, k) in enumerate(attrs):
+        p = probs[:, c0:c0 + k]
+        v = (p != -1).all(dim=-1)
+        valid.append(v)
+        pv = p[v]
+        pred = pv.argmax(dim=-1) if len(pv) else torch.zeros(0, dtype=torch.long)      # first maximum wins
+        preds.append(pred)
+        counts[ATTR_STRIDE * a] = int(v.sum())
+        for c in range(k):
+            counts[ATTR_STRIDE * a + OFF_HIST + c] = int((pred == c).sum())
+        counts[ATTR_STRIDE * a + OFF_BELOW] = int((pv.max(dim=-1).values < 0.8).sum()) if len(pv) else 0
+    # one classifier head produces every attribute of an image: the reference's per-attribute masks coincide
+    assert all(torch.equal(valid[0], v) for v in valid[1:]), "attributes of one row must be valid together"
+    if attrs[0][1] == 2:
+        p1 = probs[:, attrs[0][0] + 1][valid[0]]
+        counts[OFF_P1_HI] = int(((p1 >= 0.5) * (p1 <= 1)).sum())
+        counts[OFF_P1_LO] = int(((p1 >= 0) * (p1 <= 0.5)).sum())
+        counts[OFF_P1_MID] = int(((p1 >= 0.2) * (p1 <= 0.8)).sum())
+        if len(attrs) >= 2:
+            for g in range(2):
+                for r in range(attrs[1][1]):
+                    counts[OFF_JOINT + 4 * g + r] = int(((preds[0] == g) * (preds[1] == r)).sum())
+            counts[OFF_JOINT_VALID] = int((valid[0] & valid[1]).sum())
+    return counts
+
+
+def _freq(c, n):
+    """``(mask).float().mean()``: the fp32 sum of c ones divided by n in fp32 (NaN for the empty selection, as torch's mean)."""
+    return torch.tensor(float(c), dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)
+
+
+def _pairwise_gap(freqs):
+    """Mean |f_i - f_j| over the ordered pairs i != j, in fp32 and in row-major order: what the reference's
+    ``cdist(f, f, p=1)`` with the diagonal dropped, ``.mean()`` computes."""
+    f = torch.stack(freqs)
+    n = f.shape[0]
+    d = (f[:, None] - f[None, :]).abs()
+    return d[~torch.eye(n, dtype=torch.bool)].reshape(n, n - 1).mean().item()
+
+
+def gap_metrics(experiment, counts):
+    """The reference's validation numbers of ``experiment`` from the integer counts of ``tally_host`` / ``ops.eval_tally``."""
+    c = [int(v) for v in (counts.tolist() if hasattr(counts, "tolist") else counts)]
+    A = lambda a: (c[ATTR_STRIDE * a], c[ATTR_STRIDE * a + OFF_HIST:ATTR_STRIDE * a + OFF_HIST + 4], c[ATTR_STRIDE * a + OFF_BELOW])
+    if experiment in ("exp-1", "exp-2"):
+        n = c[0]
+        gap = (_freq(c[OFF_P1_HI], n) - _freq(c[OFF_P1_LO], n)).item()
+        return {"gender_gap": gap, "gender_gap_abs": abs(gap), "gender_pred_between_0.2_0.8": abs(_freq(c[OFF_P1_MID], n).item())}
+    if experiment == "exp-6":
+        n, h, below = A(0)
+        f = [_freq(h[k], n) for k in range(4)]
+        out = {f"race{k}_freq": f[k].item() for k in range(4)}
+        out.update({"race_gap": _pairwise_gap(f), "race_pred_below_0.8": _freq(below, n).item()})
+        return out
+    if experiment in ("exp-3", "exp-4", "exp-5"):
+        ng, hg, bg = A(0)
+        nr, hr, br = A(1)
+        out = {"gender_gap": abs(_freq(hg[1], ng) - _freq(hg[0], ng)).item(), "gender_pred_below_0.8": _freq(bg, ng).item(),
+               "race_gap": _pairwise_gap([_freq(hr[k], nr) for k in range(4)]), "race_pred_below_0.8": _freq(br, nr).item(),
+               "gender_race_gap": _pairwise_gap([_freq(c[OFF_JOINT + k], c[OFF_JOINT_VALID]) for k in range(8)])}
+        if experiment == "exp-4":
+            na, ha, ba = A(2)
+            a0, a1 = _freq(ha[0], na).item(), _freq(ha[1], na).item()
+            out.update({"age_young_freq": a0, "age_old_freq": a1, "age_pred_below_0.8": _freq(ba, na).item(),
+                        "age_gap": (abs(a0 - 0.75) + abs(a1 - 0.25)) / 2})
+        return out
+    raise ValueError(f"no validation metrics for {experiment}")
+
+
+def grid_shape(N, H, W):
+    rows = int(math.sqrt(N))
+    cols = math.ceil(N / rows)
+    return rows, cols, (rows * (H + 2 * FRAME), cols * (W + STRIP + 2 * FRAME), 3)
+
+
+def grid_order(preds, maxprob, n_classes=2):
+    """Tile order of ``plot_in_grid``: exp-1 shows class 1 then class 0 (:163-173), exp-6 classes 0..3 (:160-178), each from the most to the
+    least confident, then the images without a face in index order.  Ties keep the index order."""
+    preds, maxprob = np.asarray(preds), np.asarray(maxprob, dtype=np.float32)
+    classes = [1, 0] if n_classes == 2 else list(range(n_classes))
+    out = []
+    for cl in classes:
+        idx = np.nonzero(preds == cl)[0]
+        out += list(idx[np.argsort(-maxprob[idx], kind="stable")])
+    out += list(np.nonzero(preds == -1)[0])
+    return np.asarray(out, dtype=np.int32)
+
+
+def grid_host(images, order, boxes, preds, maxprob, palette):
+    """The numpy statement of ``fd_eval_grid_u8``: images [N,3,H,W] in [-1,1] (any float dtype), order [N] tile -> image, boxes [N,4]
+    (x0,y0,x1,y1, both ends drawn), preds [N] (-1 = no face), maxprob [N] fp32, palette [(r,g,b)] indexed by pred + 1 -> uint8 grid.
+    Per tile, in the reference's drawing order: pixels ``(x*0.5+0.5)*255`` truncated; a 4-pixel outline of the box in the class colour,
+    clipped to the image; a 50-pixel strip of the class colour on the left; when p < 1 a white bar over columns 0..50 (the image's first
+    column included) and rows 0..int((1-p)*512); a 10-pixel black frame.  Tiles past N are white."""
+    N, _, H, W = images.shape
+    rows, cols, shape = grid_shape(N, H, W)
+    x = torch.as_tensor(images).float() * 0.5 + 0.5
+    pix = x.mul(255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().cpu().numpy()
+    palette = np.asarray(palette, dtype=np.uint8)
+    th, tw = H + 2 * FRAME, W + STRIP + 2 * FRAME
+    grid = np.full(shape, 255, dtype=np.uint8)
+    for t in range(N):
+        i = int(order[t])
+        col = palette[int(preds[i]) + 1]
+        im = pix[i].copy()
+        x0, y0, x1, y1 = (int(v) for v in boxes[i])
+        yy, xx = np.mgrid[0:H, 0:W]
+        # PIL's outline of width 4: rows y0..y0+3 and y1-3..y1 over x0..x1; columns x0..x0+3 and x1-3..x1 over the rows from ya = y0+4 towards
+        # yb = y1-3, yb itself left out, in either direction (a box lower than 8 pixels -- the no-face box -1,-1,-1,-1 -- still gets those columns)
+        hor = (((yy >= y0) & (yy < y0 + BOX_WIDTH)) | ((yy <= y1) & (yy > y1 - BOX_WIDTH))) & (xx >= x0) & (xx <= x1)
+        ya, yb = y0 + BOX_WIDTH, y1 - BOX_WIDTH + 1
+        lo, hi = (ya, yb - 1) if ya <= yb else (yb + 1, ya)
+        ver = (((xx >= x0) & (xx < x0 + BOX_WIDTH)) | ((xx <= x1) & (xx > x1 - BOX_WIDTH))) & (yy >= lo) & (yy <= hi)
+        im[hor | ver] = col
+        tile = np.zeros((th, tw, 3), dtype=np.uint8)
+        inner = tile[FRAME:FRAME + H, FRAME:FRAME + STRIP + W]
+        inner[:, :STRIP] = col
+        inner[:, STRIP:] = im
+        p = float(np.float32(maxprob[i]))
+        if p < 1:
+            inner[:min(int((1 - p) * 512), H - 1) + 1, :STRIP + 1] = 255
+        r, c = divmod(t, cols)
+        grid[r * th:(r + 1) * th, c * tw:(c + 1) * tw] = tile
+    return grid
+
+
+# ------------------------------------------------------------------------------------------ the two functions of the reference's loop
+def draw_val_noise(n_prompts, n_images, lat):
+    """``noises_val`` (:1660-1663): drawn on the global CPU generator, so a run with validation consumes it exactly where the reference does."""
+    return torch.randn([n_prompts, n_images, 4, lat, lat], dtype=torch.float32)
+
+
+def validation_prompts(data):
+    """``prompt_templates_test x occupations_val_set`` of the experiment data (:924)."""
+    return [p.format(occupation=o) for p in data["prompt_templates_test"] for o in data["occupations_val_set"]]
+
+
+def _frozen_pair(tr):
+    """The ``_ori`` pass's models (:1469-1474): the frozen copy of whatever is being trained (exp-2: both networks are frozen anyway)."""
+    a = tr.args
+    te = tr.eval_te if (getattr(a, "train_text_encoder", False) or tr.prefix is not None) else tr.te
+    unet = tr.eval_unet if (getattr(a, "train_unet", False) or tr.prefix is not None) else tr.unet
+    return te, unet
+
+
+def prefix_tokens_for(tr, toks):
+    """exp-2: the token tuple of the prompt with the trainer's prefix placeholders in front, as ``train.py`` builds it for the step."""
+    from .generate import prefix_tokens
+    return prefix_tokens(toks, tr.prefix.n, tr.te.config.vocab_size)
+
+
+def _generate(tr, te, unet, tokens, noises, prefix=None):
+    vb = max(int(tr.args.val_GPU_batch_size), 1)
+    enc = tr.encode_pair(te, tokens, prefix=prefix)
+    out = []
+    for j in range(0, noises.shape[0], vb):
+        x, _, _ = tr.rollout(unet, enc, noises[j:j + vb], N_DENOISING_STEPS_VAL)
+        out.append(tr.decode(x))
+    return torch.cat(out)
+
+
+def probability_table(tr, h):
+    """[N, sum k] fp32 on the device from ``classify_begin``'s handle: softmax per attribute, -1 rows where no face was found."""
+    from .step import _h2d
+    pd = torch.full((h["N"], sum(k for _, _, k in tr.attrs)), -1.0, dtype=torch.float32, device=tr.device)
+    if h["logits_dev"] is not None:
+        pd[_h2d(h["sel"], tr.device)] = torch.cat([torch.softmax(h["logits_dev"][:, c0:c0 + k], dim=-1) for _, c0, k in tr.attrs], dim=1)
+    return pd
+
+
+def _gather_dev(tr, t):
+    """All ranks' tensors concatenated in rank order on the device (``customized_all_gather``); the tensor itself on one rank."""
+    if not tr.collectives:
+        return t
+    import torch.distributed as dist
+    t = t.contiguous()
+    gl = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(gl, t)
+    return torch.cat(gl)
+
+
+def grid_inputs(pd, k0):
+    """(preds int32 [N], maxprob fp32 [N], order int32 [N]) of the first attribute (columns 0..k0-1 of the table), on the table's device, by the
+    rules of ``tally_host`` / ``grid_order``: -1 where any entry is -1, the FIRST maximum wins, classes in plot_in_grid's order (two classes: 1 then
+    0; four: 0..3), each from the most to the least confident with ties in index order, then the images without a face."""
+    p0 = pd[:, :k0]
+    valid = (p0 != -1).all(dim=-1)
+    maxprob = p0.max(dim=-1).values
+    cols = torch.arange(k0, device=pd.device).expand_as(p0)
+    arg = torch.where(p0 == maxprob[:, None], cols, torch.full_like(cols, k0)).min(dim=-1).values      # first maximum: a minimum has no tie rule to rely on
+    preds = torch.where(valid, arg, torch.full_like(arg, -1)).to(torch.int32)
+    group = torch.where(valid, (1 - arg) if k0 == 2 else arg, torch.full_like(arg, k0))
+    by_conf = torch.sort(-maxprob, stable=True).indices
+    order = by_conf[torch.sort(group[by_conf], stable=True).indices].to(torch.int32)
+    return preds.contiguous(), maxprob.float().contiguous(), order.contiguous()
+
+
+def device_grid(tr, images, boxes, pd):
+    """The annotated grid of the first attribute's predictions (uint8 on the device): predictions, confidences and the tile order are derived
+    from the device table (``grid_inputs``), the painting is one launch of ``ops.eval_grid``."""
+    from . import ops
+    k0 = tr.attrs[0][2]
+    preds, maxprob, order = grid_inputs(pd, k0)
+    palette = torch.tensor(PALETTE_GENDER if k0 == 2 else PALETTE_RACE, dtype=torch.uint8, device=images.device)
+    return ops.eval_grid(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, maxprob, palette)
+
+
+def _json_safe(v):
+    """NaN (an empty valid set) is written as null: the line stays valid JSON for strict parsers."""
+    if isinstance(v, dict):
+        return {k: _json_safe(x) for k, x in v.items()}
+    return None if isinstance(v, float) and math.isnan(v) else v
+
+
+def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="metrics", imgs_dir=None, log=print):
+    """``evaluate_process`` (:1449-1571) for the weights the models currently hold.  ``which``: "main" or "EMA" -- it selects exp-2's prefix
+    vectors; the LoRA operands are switched by ``evaluation_step``.  ``prompts_tokens``: [(prompt, token tuple)]; ``noises`` [P, n, 4, h, w] on the
+    host.  Returns [{metric: value}] per prompt (every rank tallies the same gathered table; only rank 0 prints and writes).  In the JSON line a
+    NaN (no valid row) is written as null.  With ``mode="grids"`` rank 0 also writes
+    ``eval_{name}_{step}_{prompt}_{ori|generated}.jpg``; with ``"metrics"`` the frozen pass, which only feeds its grid, is not generated."""
+    from . import ops
+    tr = trainer
+    logs = []
+    tr.last_eval_counts = []          # the int32 counts behind ``logs``, per prompt (what the tests compare with the host tally)
+    te_o, unet_o = _frozen_pair(tr)
+    for (prompt, toks), noises_i in zip(prompts_tokens, noises):
+        nd = noises_i.to(tr.device, torch.float32)
+        toks_gen, toks_ori, pv = toks, toks, None
+        if tr.prefix is not None:
+            toks_gen = prefix_tokens_for(tr, toks)
+            toks_ori = (toks[0], toks[1], toks[2], torch.ones_like(toks[3]))
+            pv = tr.prefix.vectors(ema=(which == "EMA"))
+        passes = ([("ori", te_o, unet_o, toks_ori, None)] if mode == "grids" else []) + [("generated", tr.te, tr.unet, toks_gen, pv)]
+        for tag, te, unet, tk, prefix in passes:
+            images = _generate(tr, te, unet, tk, nd, prefix=prefix)
+            h = tr.classify_begin(images)
+            pd = _gather_dev(tr, probability_table(tr, h))
+            if tag == "generated":
+                counts = ops.eval_tally(pd, table_attrs(tr.attrs)).cpu()          # the evaluation's read-back: 32 integers
+                tr.last_eval_counts.append(counts)
+                logs.append(gap_metrics(tr.experiment, counts))
+            if mode == "grids":
+                images_all, boxes_all = _gather_dev(tr, images), _gather_dev(tr, h["boxes"].to(tr.device, torch.int32))
+                if tr.rank == 0:
+                    from PIL import Image
+                    os.makedirs(imgs_dir, exist_ok=True)
+                    grid = device_grid(tr, images_all, boxes_all, pd).cpu().numpy()
+                    Image.fromarray(grid).save(os.path.join(imgs_dir, f"eval_{name}_{step}_{prompt}_{tag}.jpg"), quality=25)
+    if tr.rank == 0 and log is not None:
+        keys = list(logs[0].keys()) if logs else []
+        log(json.dumps(_json_safe({"eval": name, "step": step, "per_prompt": {p: m for (p, _), m in zip(prompts_tokens, logs)},
+                                   "mean": {k: float(np.array([m[k] for m in logs]).mean()) for k in keys}})))
+    return logs
+
+
+def evaluation_step(trainer, tokenizer, prompts_val, step, noises_val=None, mode="metrics", imgs_dir=None, log=print):
+    """``evaluation_step`` (:1659-1690): validation noise from the global CPU generator, the live weights ("main"), then the EMA weights ("EMA").
+    The EMA pass rewrites the 16-bit LoRA operand copies from ``bank.ema`` and restores them from ``bank.flat``: the fp32 parameters, their EMA and
+    the optimiser moments are never written."""
+    tr = trainer
+    a = tr.args
+    if noises_val is None:
+        noises_val = draw_val_noise(len(prompts_val), a.val_images_per_prompt_GPU, tr.unet.config.sample_size)
+    tr.finish_r2_prefetch()          # the frozen U-Net may hold a prefetched rollout of the next step: completed first, not dropped
+    pt = [(p, tokenizer(p)) for p in prompts_val]
+    out = {"main": evaluate_process(tr, "main", "main", pt, noises_val, step, mode=mode, imgs_dir=imgs_dir, log=log)}
+    nets = [n for n, on in ((tr.unet, getattr(a, "train_unet", False)), (tr.te, getattr(a, "train_text_encoder", False)))
+            if on and tr.prefix is None and n.lora_bank is not None]
+    try:
+        for n in nets:
+            n.refresh_lora(ema=True)
+        out["EMA"] = evaluate_process(tr, "EMA", "EMA", pt, noises_val, step, mode=mode, imgs_dir=imgs_dir, log=log)
+    finally:
+        for n in nets:
+            n.refresh_lora()
+    if tr._side is not None and "r2" in tr._side:
+        tr._side["r2"].wait_stream(torch.cuda.current_stream())      # the next step's frozen rollout starts behind the validation's use of that U-Net
+    return out

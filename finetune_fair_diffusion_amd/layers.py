@@ -114,9 +114,11 @@ class LoRAPair:
         return self.bank.view(self.dn, self.bank.accum), self.bank.view(self.un, self.bank.accum)
 
 
-def refresh_pairs(pairs, scale=1.0):
+def refresh_pairs(pairs, scale=1.0, ema=False):
     """Rewrites the 16-bit operand copies of ``pairs`` from their fp32 parameters: ONE call of ``fd_lora_refresh_multi`` (16 pairs per launch)
-    instead of ~8 tiny torch launches per pair (128 pairs in the U-Net: 10 ms of host-bound time per optimiser step before)."""
+    instead of ~8 tiny torch launches per pair (128 pairs in the U-Net: 10 ms of host-bound time per optimiser step before).
+    ``ema=True`` reads the bank's EMA twin instead (validation of the EMA weights, evaluation.py): only the source pointers differ, no fp32
+    buffer is written; a second call with ``ema=False`` restores the live operands bit for bit."""
     import ctypes
     from . import lib as _lib
     pairs = list(pairs)
@@ -126,7 +128,8 @@ def refresh_pairs(pairs, scale=1.0):
     for d, p in zip(arr, pairs):
         if p.down16 is None:
             p.place()
-        dn, up = p.bank.view(p.dn), p.bank.view(p.un)
+        buf = p.bank.ema if ema else None
+        dn, up = p.bank.view(p.dn, buf), p.bank.view(p.un, buf)
         d.down, d.up = dn.data_ptr(), up.data_ptr()
         d.d16, d.ld_d16, d.dT16, d.ld_dT16 = p.down16.data_ptr(), p.down16.stride(0), p.downT16.data_ptr(), p.downT16.stride(0)
         d.u16, d.ld_u16, d.uT16, d.ld_uT16 = p.up16.data_ptr(), p.up16.stride(0), p.upT16.data_ptr(), p.upT16.stride(0)

@@ -791,6 +791,38 @@ def ot_expected_targets(cost, counts, weights, return_seats=False):
     return (t, u, st) if return_seats else (t, u)
 
 
+# ----------------------------------------------------------------------------- validation tail (csrc/evaluate.hip)
+def eval_tally(probs, attrs):
+    """Counts of one validation prompt (``fd_eval_tally``; layout: include/fairdiff_hip.h, evaluation.py): probs [N, ld] fp32 on the device with -1
+    rows for "no face", attrs [(first column, k)] -> int32 [32] on the device.  One launch, nothing read back."""
+    assert probs.dtype == F32 and probs.dim() == 2 and probs.stride(1) == 1, (probs.dtype, probs.shape, probs.stride())
+    n = len(attrs)
+    c0 = (ctypes.c_int32 * max(n, 1))(*[int(a[0]) for a in attrs])
+    k = (ctypes.c_int32 * max(n, 1))(*[int(a[1]) for a in attrs])
+    counts = torch.empty(32, dtype=torch.int32, device=probs.device)
+    _call("fd_eval_tally", _p(probs), probs.shape[0], probs.stride(0) if probs.shape[0] > 1 else probs.shape[1], c0, k, n, _p(counts), _stream())
+    return counts
+
+
+def eval_grid(images, order, boxes, preds, maxprob, palette, rows=None, cols=None, out=None):
+    """The annotated uint8 grid of ``plot_in_grid`` in one launch (``fd_eval_grid_u8``): images [N,3,H,W] working dtype in [-1,1]; order / preds [N]
+    and boxes [N,4] int32, maxprob [N] fp32, palette [<= 6, 3] uint8 (pred -1, 0, 1, ...), all on the device -> [rows*(H+20), cols*(W+70), 3] uint8."""
+    N, _, H, W = images.shape
+    rows = int(math.sqrt(N)) if rows is None else rows
+    cols = math.ceil(N / rows) if cols is None else cols
+    pal = torch.full((6, 3), 255, dtype=torch.uint8, device=images.device)
+    pal[:palette.shape[0]] = palette
+    for t, dt, shp in ((order, torch.int32, (N,)), (boxes, torch.int32, (N, 4)), (preds, torch.int32, (N,)), (maxprob, F32, (N,))):
+        assert t.dtype == dt and tuple(t.shape) == shp and t.is_contiguous(), (t.dtype, t.shape, shp)
+    shape = (rows * (H + 20), cols * (W + 70), 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=images.device)
+    # the entry point cannot see the size of the buffer it fills
+    assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape, (out.dtype, out.shape, shape)
+    _call("fd_eval_grid_u8", _p(_chk(images)), _p(order), _p(boxes), _p(preds), _p(maxprob), _p(pal), _p(out), N, H, W, rows, cols, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- text-encoder attention
 def small_attn_fwd(q, k, v, key_valid, B, H, T, d, scale, causal=True, save_p=False):
     o = torch.empty_like(q)

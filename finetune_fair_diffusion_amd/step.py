@@ -668,6 +668,20 @@ class FairnessTrainer:
         dist.all_gather(gl, pg)
         return torch.cat(gl).cpu()          # concatenated on the device, ONE copy to the host (it was one copy per rank)
 
+    def finish_r2_prefetch(self):
+        """Runs the remaining denoising steps of a prefetched next-step R2 rollout on its stream and makes the current stream wait for them.  The
+        rollout's time embeddings and prompt projections live on the frozen U-Net object: whoever uses that U-Net between two training steps (the
+        validation passes) calls this first, so the prefetch is completed instead of dropped -- the next step finds all S steps done."""
+        pre = self._r2_pre
+        if pre is None:
+            return
+        side = self._side_stream("r2")
+        with torch.cuda.stream(side):
+            for _ in pre["gen"]:
+                pass
+        pre["k"] = pre["S"]
+        torch.cuda.current_stream().wait_stream(side)
+
     def allreduce_grads(self):
         """(2) ONE all-reduce(SUM) per flat fp32 LoRA-gradient buffer (RCCL over xGMI on the GPU box)."""
         if getattr(self, "collectives", self.world > 1):

@@ -51,9 +51,9 @@ class CLIPTextModel:
         self.refresh_lora()
         return self.lora_bank
 
-    def refresh_lora(self):
+    def refresh_lora(self, ema=False):
         from .layers import refresh_pairs
-        refresh_pairs([lo for L in self.layers for lo in L["lora"].values()])
+        refresh_pairs([lo for L in self.layers for lo in L["lora"].values()], ema=ema)
 
     def load_state_dict(self, sd, strict=False):
         if self.lora_bank is not None:

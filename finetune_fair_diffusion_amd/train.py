@@ -5,8 +5,14 @@
 
 Same flags, YAML overlay, seeding (``set_seed(seed, device_specific=True)`` :693, prompt order from
 ``random.seed(seed+1)`` :914-921, S drawn on rank 0 from range(19,24) and broadcast :1779-1781, per-rank CPU noise
-:1746-1749), checkpoint cadence (:2050-2068) and resume (:1697-1725) as the reference; wandb/plots/evaluation grids are
+:1746-1749), checkpoint cadence (:2050-2068) and resume (:1697-1725) as the reference; wandb and the training plots are
 replaced by one JSON line per step on rank 0.  One process per GPU; RCCL through torch.distributed ("nccl").
+
+Validation (``evaluation_step`` :1659-1690) is opt-in: ``--validation metrics`` runs it at step 0 and every ``--evaluate_every_n_iter`` steps for
+the live and the EMA weights and prints one more JSON line per pass (``{"eval": "main"|"EMA", "step", "per_prompt", "mean"}`` with the
+reference's gap metrics); ``--validation grids`` also writes the annotated image grids to ``<output_dir>/imgs``.  Its noise is drawn from the
+global CPU generator at the reference's points, so the training noise of such a run is the reference's with evaluation enabled.  With
+``--validation off`` (default) nothing changes.
 """
 import json
 import math
@@ -24,7 +30,8 @@ from .cli import parse_args
 from .factory import SD15, TINY, build_trainer, synthetic_tokens
 
 SYNTHETIC_PROMPTS = dict(prompt_templates_train=["a photo of the face of a {occupation}, a person", "a portrait of a {occupation}, a person"],
-                         occupations_train_set=["doctor", "teacher", "engineer", "chef", "pilot", "nurse"])
+                         occupations_train_set=["doctor", "teacher", "engineer", "chef", "pilot", "nurse"],
+                         prompt_templates_test=["a photo of the face of a {occupation}, a person"], occupations_val_set=["lawyer", "farmer"])
 
 
 class HashTokenizer:
@@ -59,15 +66,42 @@ class CLIPTokenizerAdapter:
         return t.input_ids[0], t.attention_mask[0], u.input_ids[0], u.attention_mask[0]
 
 
-def load_prompts(args):
-    """Occupation prompts (:905-908); exp-5 mixes in three more files at 6x / 20x / 4x (exp-5 :934-947)."""
+def _occupation_data(args):
     if os.path.exists(args.prompt_occupation_path):
         with open(args.prompt_occupation_path, "r") as f:
-            data = json.load(f)
-    elif getattr(args, "synthetic", False):
-        data = SYNTHETIC_PROMPTS
-    else:
-        raise FileNotFoundError(f"{args.prompt_occupation_path} (pass --synthetic to run without the reference's data.zip)")
+            return json.load(f)
+    if getattr(args, "synthetic", False):
+        return SYNTHETIC_PROMPTS
+    raise FileNotFoundError(f"{args.prompt_occupation_path} (pass --synthetic to run without the reference's data.zip)")
+
+
+def draw_step_noise(B, lat, num_denoising_steps=0):
+    """One step's host randomness in the reference's order (:1746-1749, :1779): CPU noise, then the number of denoising steps."""
+    noises = torch.randn([B, 4, lat, lat], dtype=torch.float32)          # CPU generator, differs by rank (:1746-1749)
+    return noises, num_denoising_steps or random.choices(range(19, 24), k=1)[0]
+
+
+def peek_draw(draw, before=None):
+    """What ``draw()`` WILL return, without consuming the generators: the draw is made on saved generator states that are restored afterwards,
+    so the run's random streams -- and the RNG state a checkpoint stores -- are exactly those of a loop without look-ahead.  ``before``: draws
+    that the loop will make between now and that ``draw`` (the validation noise of an evaluation that falls between the two steps)."""
+    st = (random.getstate(), np.random.get_state(), torch.get_rng_state())
+    try:
+        if before is not None:
+            before()
+        return draw()
+    finally:
+        random.setstate(st[0]); np.random.set_state(st[1]); torch.set_rng_state(st[2])
+
+
+def evaluation_due(validation, global_step, every):
+    """The reference's two points (:1739-1740, :2047-2048): before the first step of a fresh run, and after a step whose number divides."""
+    return validation != "off" and every > 0 and global_step % every == 0
+
+
+def load_prompts(args):
+    """Occupation prompts (:905-908); exp-5 mixes in three more files at 6x / 20x / 4x (exp-5 :934-947)."""
+    data = _occupation_data(args)
     prompts = [p.format(occupation=o) for p in data["prompt_templates_train"] for o in data["occupations_train_set"]]
     extra = [("prompt_occupation_w_style_and_context_path", 6), ("prompt_personal_descroptor_path", 20), ("prompt_sports_path", 4)]
     if all(hasattr(args, k) for k, _ in extra):
@@ -171,23 +205,32 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
             first_epoch, resume_step = global_step // steps_per_epoch, global_step % steps_per_epoch
     lat = cfgs["unet"].sample_size
     B = args.train_images_per_prompt_GPU
+    validation = getattr(args, "validation", "off")
+    prompts_val = []
+    if validation != "off":
+        from . import evaluation
+        prompts_val = evaluation.validation_prompts(_occupation_data(args))
+        imgs_dir = os.path.join(args.output_dir, "imgs")
+
+    def draw_val():
+        return evaluation.draw_val_noise(len(prompts_val), args.val_images_per_prompt_GPU, lat)
+
+    def evaluate(at_step):
+        evaluation.evaluation_step(trainer, tokenizer, prompts_val, at_step, noises_val=draw_val(), mode=validation, imgs_dir=imgs_dir, log=log or print)
+
     def draw(data_idx):
         """The per-step host inputs in the reference's order (:1746-1749, :1779): prompt, CPU noise, number of denoising steps."""
         prompt = prompts_train[data_idx]
-        noises = torch.randn([B, 4, lat, lat], dtype=torch.float32)          # CPU generator, differs by rank (:1746-1749)
-        S = [args.num_denoising_steps or random.choices(range(19, 24), k=1)[0]]
+        noises, S0 = draw_step_noise(B, lat, args.num_denoising_steps)
+        S = [S0]
         if world > 1:
             dist.broadcast_object_list(S, src=0)
         return prompt, noises, S[0]
 
-    def peek(data_idx):
-        """What ``draw`` WILL return for the next step, without consuming the generators: the draw is made on saved generator states that are
-        restored afterwards, so the run's random streams -- and the RNG state a checkpoint stores -- are exactly those of a loop without look-ahead."""
-        st = (random.getstate(), np.random.get_state(), torch.get_rng_state())
-        try:
-            return draw(data_idx)
-        finally:
-            random.setstate(st[0]); np.random.set_state(st[1]); torch.set_rng_state(st[2])
+    def peek(data_idx, eval_between=False):
+        """``draw`` of the NEXT step on saved generator states (``peek_draw``); when an evaluation falls between this step and the next, its
+        validation noise is drawn first on those states, as the loop will."""
+        return peek_draw(lambda: draw(data_idx), before=draw_val if eval_between else None)
 
     def r2_tokens(toks):
         # exp-2 (:1954): the original side sees the plain prompt, its empty prompt encoded without a padding mask
@@ -198,6 +241,8 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
     for i, (epoch, step, data_idx) in enumerate(plan):
         if global_step >= args.max_train_steps:
             break
+        if global_step == 0 and evaluation_due(validation, 0, args.evaluate_every_n_iter):      # :1739-1740, before the first training noise
+            evaluate(0)
         prompt, noises, S0 = draw(data_idx)
         S = [S0]
         t0 = time.time()
@@ -205,7 +250,7 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
         # the next step's inputs, so that its frozen-model rollout can start underneath this step's tail (step.py, r2_prefetch_steps)
         nxt = None
         if i + 1 < len(plan) and global_step + 1 < args.max_train_steps and os.environ.get("FD_NO_R2_PREFETCH") is None:
-            p_n, noises_n, S_n = peek(plan[i + 1][2])
+            p_n, noises_n, S_n = peek(plan[i + 1][2], evaluation_due(validation, global_step + 1, args.evaluate_every_n_iter))
             nxt = dict(tokens_ori=r2_tokens(tokenizer(p_n)), noises=noises_n, S=S_n)
         if trainer.prefix is not None:
             # exp-2 (:1846, :1895, :1954, :2001): the finetuned side sees "".join(prefix_tokens) + prompt with the pipeline's negative
@@ -226,6 +271,8 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
                        p_class1_mean=float(out["probs"][:, 1][out["probs"][:, 1] != -1].mean()) if bool((out["probs"] != -1).any()) else None,
                        seconds=round(time.time() - t0, 3))
             (log or print)(json.dumps(rec))
+        if evaluation_due(validation, global_step, args.evaluate_every_n_iter):      # :2047-2048
+            evaluate(global_step)
         # checkpoints (:2050-2068): rank 0 cleans up and writes the shared state, every rank adds its own RNG streams
         if global_step % args.checkpointing_steps == 0:
             if rank == 0 and args.checkpoints_total_limit is not None:

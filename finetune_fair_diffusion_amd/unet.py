@@ -404,9 +404,9 @@ class UNet2DConditionModel:
         self.refresh_lora()
         return self.lora_bank
 
-    def refresh_lora(self):
+    def refresh_lora(self, ema=False):
         from .layers import refresh_pairs
-        refresh_pairs([p for t in self.transformers for lo in (t.lora1, t.lora2) if lo is not None for p in lo.pairs()])
+        refresh_pairs([p for t in self.transformers for lo in (t.lora1, t.lora2) if lo is not None for p in lo.pairs()], ema=ema)
 
     @property
     def lean_record(self):

@@ -335,6 +335,32 @@ int fd_ot_assign_sum(const double* cost, const int32_t* counts, float* plan, int
 int fd_ot_expected_targets(const double* cost, const int32_t* counts, const double* weights, int32_t* seats, int32_t* targets, double* uncertainty,
                            int N, int K, int S, void* stream);
 
+/* ---- in-training validation (evaluation.py; exp-1-debias-gender/1-main-debias.py evaluate_process :1449-1571, plot_in_grid :151-217;
+ * get_evaluate_metrics of exp-3/5 :1716-1749, exp-4 :1780-1821, exp-6 :1624-1637).  Additive: FD_ABI_VERSION is unchanged. */
+#define FD_EVAL_MAX_ATTR 3
+#define FD_EVAL_MAX_K 4
+#define FD_EVAL_COUNTS 32          /* int32 entries fd_eval_tally writes */
+#define FD_EVAL_ATTR_STRIDE 6      /* attribute a at 6*a: n_valid, hist[0..3] of the argmax (first maximum wins), count(max < 0.8) */
+#define FD_EVAL_OFF_P1_HI 18       /* two-class attribute 0, rows valid in it: count(p1 >= 0.5 && p1 <= 1) */
+#define FD_EVAL_OFF_P1_LO 19       /* count(p1 >= 0 && p1 <= 0.5): a row with p1 == 0.5 counts in both */
+#define FD_EVAL_OFF_P1_MID 20      /* count(0.2 <= p1 <= 0.8) */
+#define FD_EVAL_OFF_JOINT 21       /* 21 + 4*g + r: rows valid in attributes 0 (two classes) and 1 with argmax g and r; zero without attribute 1 */
+#define FD_EVAL_OFF_JOINT_VALID 29 /* rows valid in both; entries 30, 31 are zero */
+#define FD_EVAL_PALETTE 6          /* colours of fd_eval_grid_u8: pred -1..4 */
+/* probs [N, ld] fp32 on the device: the probability table of N images, attribute a in columns attr_c0[a] .. attr_c0[a] + attr_k[a] - 1; a row is
+ * valid for an attribute iff none of its k entries is -1 ("no face").  attr_c0 / attr_k are HOST arrays of n_attr entries.  counts [FD_EVAL_COUNTS]
+ * int32 on the device, every entry written (no zeroing by the caller); integer accumulation: exact and order-free.  Comparisons are fp32 against the
+ * fp32 value of the literal.  N 0..2^20, n_attr 1..3, k 1..4, columns inside ld; anything else is refused and nothing is launched. */
+int fd_eval_tally(const float* probs, int N, int ld, const int32_t* attr_c0, const int32_t* attr_k, int n_attr, int32_t* counts, void* stream);
+/* The whole annotated grid of plot_in_grid in one launch: images [N,3,H,W] working dtype in [-1,1] -> grid [rows*(H+20), cols*(W+70), 3] uint8
+ * (4-byte aligned).  Tile i shows image order[i]: pixels (x*0.5+0.5)*255 truncated (two fp32 roundings); the outline of boxes[order[i]] = x0,y0,x1,y1
+ * (both ends drawn, 4 pixels wide, PIL's rule) in the class colour palette[pred+1]; a 50-pixel strip of that colour on the left, and when
+ * maxprob < 1 a white bar over columns 0..50 and rows 0..int((1-maxprob)*512); a 10-pixel black frame.  Tiles past N are white.  The reference's
+ * index text (a font file outside both trees) is not drawn.  order / boxes [N,4] / preds [N] int32, maxprob [N] fp32, palette [FD_EVAL_PALETTE,3]
+ * uint8 on the device.  rows*cols holds N tiles with at most the last row partly filled; N, H, W 1..4096. */
+int fd_eval_grid_u8(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const float* maxprob, const uint8_t* palette,
+                    uint8_t* grid, int N, int H, int W, int rows, int cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
