@@ -1,7 +1,8 @@
 """Static inspection of the gfx950 code objects inside a built libfairdiff_hip*.so (build-time / test-time tool, no GPU needed):
 splits the library's .hip_fatbin into its per-translation-unit offload bundles, unbundles the gfx950 ELF of each and returns the
 disassembly and the kernel resource notes.  Used by tests/test_cpu.py to hold two build invariants: no packed-fp32 VALU instruction in any
-shipped kernel ("the round-3 hazard"), and the register / scratch budgets of the hot kernels."""
+shipped kernel ("the round-3 hazard"), and the register / scratch budgets of the hot kernels.
+``python codeobj.py --diff OLD.so NEW.so`` compares two builds kernel by kernel (how a refactor of the GEMM family shows that it left the ISA alone)."""
 import os
 import re
 import subprocess
@@ -70,8 +71,54 @@ def packed_f32_sites(lib_path):
     return sites
 
 
+GEMM_FAMILY = re.compile(r"gemm_\w*kernel|conv_halo_kernel|splitk_reduce_kernel")
+_SYMBOL = re.compile(r"^[0-9a-f]+ <(\S+)>:")
+_ADDRESS = re.compile(r"^\s*[0-9a-f]+:\s+")
+
+
+def kernel_instructions(lib_path):
+    """-> {kernel symbol: instruction text} over all gfx950 code objects of the library: the disassembly split at the ``<symbol>:`` lines, one
+    instruction per line, address column and trailing ``//`` comments (address + encoding) stripped."""
+    out = {}
+    for _, co in code_objects(lib_path):
+        cur = None
+        for ln in disassembly(co).splitlines():
+            m = _SYMBOL.match(ln)
+            if m:
+                cur = out.setdefault(m.group(1), [])
+            elif cur is not None:
+                ln = _ADDRESS.sub("", ln.split("//")[0]).strip()
+                if ln:
+                    cur.append(ln)
+    return {k: "\n".join(v) for k, v in out.items()}
+
+
+def diff(old_lib, new_lib):
+    """Prints, per kernel symbol, identical / differs (instruction counts, resources) / only in OLD|NEW; -> number of GEMM-family symbols not identical."""
+    old, new = kernel_instructions(old_lib), kernel_instructions(new_lib)
+    res = {}
+    for tag, lib in (("old", old_lib), ("new", new_lib)):
+        for _, co in code_objects(lib):
+            for n, r in kernel_resources(co).items():
+                res[tag, n] = r
+    bad = 0
+    for sym in sorted(set(old) | set(new)):
+        if sym not in new or sym not in old:
+            verdict = "only in OLD" if sym in old else "only in NEW"
+        elif old[sym] == new[sym]:
+            verdict = "identical"
+        else:
+            verdict = f"differs ({old[sym].count(chr(10)) + 1} -> {new[sym].count(chr(10)) + 1} instructions)  old {res.get(('old', sym))}  new {res.get(('new', sym))}"
+        bad += verdict != "identical" and bool(GEMM_FAMILY.search(sym))
+        print(f"{verdict:12s} {sym}" if verdict == "identical" else f"{sym}: {verdict}")
+    print(f"{len(old)} -> {len(new)} symbols, {bad} GEMM-family symbols not identical")
+    return bad
+
+
 if __name__ == "__main__":
     import sys
+    if sys.argv[1:2] == ["--diff"]:
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
     for lib in sys.argv[1:]:
         s = packed_f32_sites(lib)
         print(f"{lib}: {len(s)} packed-fp32 VALU instructions" + (f", e.g. {s[0]}" if s else ""))

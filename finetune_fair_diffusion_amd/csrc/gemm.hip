@@ -145,8 +145,7 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(fd_gemm_desc p, int ntm,
                 acc[i][j] = FD_MFMA_16x16x32(bf[j], af[i], acc[i][j]);
     }
 
-    const bool lds_epi = p.out_dtype == FD_OUT_F16 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.residual || (p.ldr & 7) == 0) &&
-                         (!p.rowbias || (p.ld_rowbias & 3) == 0);
+    const bool lds_epi = FD_GEMM_LDS_EPILOGUE_OK(p);
     if (p.act == FD_ACT_GEGLU) {      // fd_gemm checked the preconditions (fp16 out, aligned, unbatched)
         __syncthreads();
         gemm_epilogue_geglu_lds<TM, TN, TM>(p, acc, smem + wave * (BM / 2) * (BN / 2 + 4), m0 + wm * (BM / 2), n0 + wn * (BN / 2), lane);
@@ -462,8 +461,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void gemm_big_kernel(fd_gemm_desc p
         }
         return;
     }
-    const bool lds_epi = p.out_dtype == FD_OUT_F16 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.residual || (p.ldr & 7) == 0) &&
-                         (!p.rowbias || (p.ld_rowbias & 3) == 0);
+    const bool lds_epi = FD_GEMM_LDS_EPILOGUE_OK(p);
     if (FD_DBG_IS(p, 3)) {   // measurement only (FD_GEMM_DBG=3): no epilogue at all
         if (acc[0][0][0] == 12345.678f) ((f16*)p.C)[0] = (f16)1.f;
     } else if (p.act == FD_ACT_GEGLU) {
@@ -519,48 +517,36 @@ static int launch_splitk_reduce(const fd_gemm_desc& d, hipStream_t s, int nsplit
     return fd_check_launch("fd_gemm(split-K reduce)");
 }
 
+// one instantiation of gemm_big_kernel: sets its LDS attribute once and launches it.  (The kernel is a template ARGUMENT so that launch_big itself names
+// the instantiations, in the order 0, 1, 2, 6, 3, 4: that order decides where each lands in the code object.)
+template <auto KERNEL, int NTHREADS, size_t LDS>
+static void launch_big_cv(const fd_gemm_desc& d, hipStream_t s, dim3 grid, int ntm, int ntn, int gn) {
+    static std::once_flag once;
+    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); });
+    hipLaunchKernelGGL(KERNEL, grid, dim3(NTHREADS), LDS, s, d, ntm, ntn, gn);
+}
+
+// cv: gemm_big_kernel's CV (0 / 1 / 2 = dense / 3x3 gathers / phase pair; 3 / 4 / 6 = the same with the statistics epilogue, 80-column wave tiles only --
+// fd_gemm checked eligibility: GemmPlan.stats_ok)
 template <int BM, int BN, int WGM, int WGN>
-static int launch_big(const fd_gemm_desc& d, hipStream_t s, int nsplit = 1) {
+static int launch_big(const fd_gemm_desc& d, hipStream_t s, int nsplit, int cv) {
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     constexpr size_t lds = (size_t)2 * (BM + BN) * 64 * sizeof(f16);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WGM, WGN, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WGM, WGN, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WGM, WGN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    // n-tiles per band: the band's B slab (gn * BN rows of K halfs, per split) should fit an XCD's L2 next to the streaming A tiles
-    static const long l2_budget = bench_env("FD_GEMM_L2_KB") ? atol(bench_env("FD_GEMM_L2_KB")) * 1024 : 3 * 1024 * 1024;
-    const long ktot = ((long)d.K + d.K2) / nsplit;
+    constexpr int nt = WGM * WGN * 64;
+    static const long l2_budget = bench_env("FD_GEMM_L2_KB") ? atol(bench_env("FD_GEMM_L2_KB")) * 1024 : GEMM_L2_BUDGET;
+    const int gn = gemm_band_ntiles(l2_budget, BN, ((long)d.K + d.K2) / nsplit, ntn);
     const int nph = (d.conv && (d.conv_mode == FD_CONV_UP2P || d.conv_mode == FD_CONV_UP2PI)) ? 4 : 1;
-    long gnl = l2_budget / ((long)BN * ktot * 2);
-    const int gn = (int)(gnl < 1 ? 1 : (gnl > ntn ? ntn : gnl));
-    if constexpr (BN / WGN == 80) {
-        if (d.gn_stats && nsplit == 1 && d.conv && d.conv_mode == FD_CONV_UP2PI) {       // the phase pair writing the interleaved result, with statistics
-            static std::once_flag once_st6;
-            std::call_once(once_st6, [] {
-                (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WGM, WGN, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            });
-            hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WGM, WGN, 6>), dim3(ntm * ntn * nph, 1), dim3(WGM * WGN * 64), lds, s, d, ntm, ntn, gn);
-            return fd_check_launch("fd_gemm(big, phase pair with statistics epilogue)");
-        }
-        if (d.gn_stats && nsplit == 1 && !(d.conv && d.conv_mode >= FD_CONV_UP2P)) {     // the statistics-epilogue instantiations (fd_gemm checked eligibility)
-            static std::once_flag once_st;
-            std::call_once(once_st, [] {
-                (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WGM, WGN, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WGM, WGN, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            });
-            if (d.conv) hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WGM, WGN, 4>), dim3(ntm * ntn, 1), dim3(WGM * WGN * 64), lds, s, d, ntm, ntn, gn);
-            else hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WGM, WGN, 3>), dim3(ntm * ntn, 1), dim3(WGM * WGN * 64), lds, s, d, ntm, ntn, gn);
-            return fd_check_launch("fd_gemm(big, statistics epilogue)");
-        }
+    const dim3 grid(ntm * ntn * nph, nsplit);
+    if (cv == 0) launch_big_cv<gemm_big_kernel<BM, BN, WGM, WGN, 0>, nt, lds>(d, s, grid, ntm, ntn, gn);
+    else if (cv == 1) launch_big_cv<gemm_big_kernel<BM, BN, WGM, WGN, 1>, nt, lds>(d, s, grid, ntm, ntn, gn);
+    else if (cv == 2) launch_big_cv<gemm_big_kernel<BM, BN, WGM, WGN, 2>, nt, lds>(d, s, grid, ntm, ntn, gn);
+    else if constexpr (BN / WGN == 80) {
+        if (cv == 6) launch_big_cv<gemm_big_kernel<BM, BN, WGM, WGN, 6>, nt, lds>(d, s, grid, ntm, ntn, gn);
+        else if (cv == 3) launch_big_cv<gemm_big_kernel<BM, BN, WGM, WGN, 3>, nt, lds>(d, s, grid, ntm, ntn, gn);
+        else launch_big_cv<gemm_big_kernel<BM, BN, WGM, WGN, 4>, nt, lds>(d, s, grid, ntm, ntn, gn);
     }
-    if (d.conv && d.conv_mode >= FD_CONV_UP2P)
-        hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WGM, WGN, 2>), dim3(ntm * ntn * nph, nsplit), dim3(WGM * WGN * 64), lds, s, d, ntm, ntn, gn);
-    else if (d.conv) hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WGM, WGN, 1>), dim3(ntm * ntn, nsplit), dim3(WGM * WGN * 64), lds, s, d, ntm, ntn, gn);
-    else hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WGM, WGN, 0>), dim3(ntm * ntn, nsplit), dim3(WGM * WGN * 64), lds, s, d, ntm, ntn, gn);
     if (nsplit > 1) return launch_splitk_reduce(d, s, nsplit);
-    return fd_check_launch("fd_gemm(big)");
+    return fd_check_launch(cv >= 3 ? "fd_gemm(big, statistics epilogue)" : "fd_gemm(big)");
 }
 
 
@@ -686,8 +672,8 @@ static int launch(const fd_gemm_desc& d, hipStream_t s) {
 bool fd_gemm_pp_eligible(const fd_gemm_desc& d);
 int fd_gemm_launch_pp(const fd_gemm_desc& d, hipStream_t s, bool prio, int bm, int nsplit);
 bool fd_conv_halo_takes(const fd_gemm_desc& d, int bm, int nsplit);     // gemm_halo.hip: stride-1 3x3 convolutions with the halo-staged A operand
-// (round 5: the persistent streaming form of the 128x320 ping-pong kernel -- policy bit 128, measured and never selected -- and the register-B experiments
-// live in scratch/ with their measurements: gemm_pps_experiment.hip, gemm_rb_experiment.hip, gemm_rbk_experiment.hip)
+// (the persistent streaming form of the 128x320 ping-pong kernel -- policy bit 128, measured and never selected -- and the register-B experiments left
+// the library in round 5: scratch/gemm_pps_experiment.hip, gemm_rb_experiment.hip, gemm_rbk_experiment.hip, with their measurements)
 // Which problems the ping-pong kernels take (bits): 1 = stride-1 3x3 convolutions on the 256x320 tile, 2 = every dense GEMM on it,
 // 4 = s_setprio around the MFMA streams, 8 = stride-1 convolutions on the 128x320 tile, 16 = dense GEMMs on it, 32 = dense 256x320 GEMMs
 // with K <= 384 and N >= 2560 only (the FF1 projections of the 64^2 level), 64 = split-K launches of the 128x320 tile too.
@@ -790,7 +776,17 @@ static int gemm_tile(const fd_gemm_desc& d) {
 // ONE dispatch decision shared by fd_gemm, fd_gemm_kernel_name and fd_gemm_stats_rows (the launcher and the name function had drifted
 // apart once): which kernel family takes the problem, with which tile / wave grid / split-K factor, and whether that kernel can write gn_stats.
 enum { GK_SKINNY, GK_GLDS, GK_BIG, GK_PP };
-struct GemmPlan { int kind, bm, bn, wgm, wgn, nsplit, cv; bool stats_ok; };
+struct GemmPlan {
+    int kind, bm, bn, wgm, wgn, nsplit, cv;
+    bool stats_ok;
+    // the CV template argument of gemm_big_kernel for this launch (st: the launch writes gn_stats)
+    int big_cv(bool st) const { return st ? (cv == 2 ? 6 : cv + 3) : cv; }
+};
+// no second K slab unless both its length and its operand are given
+static fd_gemm_desc normalise_k2(fd_gemm_desc d) {
+    if (d.K2 <= 0 || !d.A2) d.K2 = 0;
+    return d;
+}
 static GemmPlan gemm_plan(const fd_gemm_desc& d /* K2 already normalised */) {
     GemmPlan g = {};
     const int sel = gemm_tile(d), t = sel % 1000000;
@@ -812,9 +808,7 @@ static GemmPlan gemm_plan(const fd_gemm_desc& d /* K2 already normalised */) {
     }
     // the statistics epilogue lives in gemm_epilogue_lds<..., true>: 80-column wave tiles, fp16 LDS-staged epilogue, no split-K (its epilogue runs in
     // splitk_reduce_kernel), not the phase-major output of the up-sampling pair (a chunk there is not a run of pixels of one image)
-    const bool lds_epi = d.out_dtype == FD_OUT_F16 && (d.N & 7) == 0 && (d.ldc & 7) == 0 && (!d.residual || (d.ldr & 7) == 0) &&
-                         (!d.rowbias || (d.ld_rowbias & 3) == 0);
-    g.stats_ok = (g.kind == GK_PP || (g.kind == GK_BIG && g.bn / g.wgn == 80)) && g.nsplit == 1 && lds_epi && d.act != FD_ACT_GEGLU &&
+    g.stats_ok = (g.kind == GK_PP || (g.kind == GK_BIG && g.bn / g.wgn == 80)) && g.nsplit == 1 && FD_GEMM_LDS_EPILOGUE_OK(d) && d.act != FD_ACT_GEGLU &&
                  d.batch <= 1 && (d.N % 80) == 0 && (g.cv < 2 || (d.conv_mode == FD_CONV_UP2PI && (d.M & 31) == 0));
     return g;
 }
@@ -824,16 +818,16 @@ static GemmPlan gemm_plan(const fd_gemm_desc& d /* K2 already normalised */) {
 // ``splitk_reduce_kernel`` that the bench's events bracket together with the GEMM.
 extern "C" int fd_gemm_kernel_name(const fd_gemm_desc* dp, char* buf, int n) {
     FD_REQUIRE_DESC(dp, fd_gemm_desc, "fd_gemm_kernel_name");
-    fd_gemm_desc d = *dp;
-    if (d.K2 <= 0 || !d.A2) d.K2 = 0;
+    const fd_gemm_desc d = normalise_k2(*dp);
     const GemmPlan g = gemm_plan(d);
     const bool st = d.gn_stats && g.stats_ok;
     switch (g.kind) {
         case GK_PP:
-            if (fd_conv_halo_takes(d, g.bm, g.nsplit)) snprintf(buf, n, "conv_halo_kernel<%d, %d, %d, %s>", g.bm, d.W, st ? 3 : 1, (pp_mode() & 4) ? "true" : "false");
+            // (conv_halo_kernel exists in its s_setprio form only: policy bit 4 does not reach it)
+            if (fd_conv_halo_takes(d, g.bm, g.nsplit)) snprintf(buf, n, "conv_halo_kernel<%d, %d, %d, true>", g.bm, d.W, st ? 3 : 1);
             else snprintf(buf, n, "gemm_pp_kernel<%d, %d, %s>", g.bm, (d.conv ? 1 : 0) + (st ? 2 : 0), (pp_mode() & 4) ? "true" : "false");
             break;
-        case GK_BIG: snprintf(buf, n, "gemm_big_kernel<%d, %d, %d, %d, %d>", g.bm, g.bn, g.wgm, g.wgn, st ? (g.cv == 2 ? 6 : g.cv + 3) : g.cv); break;
+        case GK_BIG: snprintf(buf, n, "gemm_big_kernel<%d, %d, %d, %d, %d>", g.bm, g.bn, g.wgm, g.wgn, g.big_cv(st)); break;
         case GK_SKINNY: snprintf(buf, n, "gemm_skinny_kernel<%d, %d, 1>", g.bn / 16, d.K >= 1280 ? 4 : d.K >= 640 ? 2 : 1); break;
         default: snprintf(buf, n, "gemm_glds_kernel<%d, %d, %s>", g.bm, g.bn, d.conv ? "true" : "false"); break;
     }
@@ -844,9 +838,7 @@ extern "C" int fd_gemm_kernel_name(const fd_gemm_desc* dp, char* buf, int n) {
 // canonical 32-row chunks whatever its tile), 0 when the kernel fd_gemm would launch has none.
 extern "C" int fd_gemm_stats_rows(const fd_gemm_desc* dp) {
     FD_REQUIRE_DESC(dp, fd_gemm_desc, "fd_gemm_stats_rows");
-    fd_gemm_desc d = *dp;
-    if (d.K2 <= 0 || !d.A2) d.K2 = 0;
-    return gemm_plan(d).stats_ok ? 32 : 0;
+    return gemm_plan(normalise_k2(*dp)).stats_ok ? 32 : 0;
 }
 
 extern "C" int fd_gemm(const fd_gemm_desc* dp, void* stream) {
@@ -863,7 +855,8 @@ extern "C" int fd_gemm(const fd_gemm_desc* dp, void* stream) {
         FD_REQUIRE(!d.conv, "fd_gemm: second K-slab not supported with conv gather");
         FD_REQUIRE(d.A2 && d.B2 && (d.K2 & 7) == 0 && (d.lda2 & 7) == 0 && (d.ldb2 & 7) == 0, "fd_gemm: bad second slab");
         FD_REQUIRE(d.batch <= 1, "fd_gemm: second slab is not batched");
-    } else d.K2 = 0;
+    }
+    d = normalise_k2(d);
     if (d.conv) {
         const bool up_fwd = d.conv_mode == FD_CONV_UP2P || d.conv_mode == FD_CONV_UP2PI;
         const int ntap = up_fwd ? 4 : d.conv_mode == FD_CONV_UP2P_BWD ? 16 : 9;
@@ -901,15 +894,17 @@ extern "C" int fd_gemm(const fd_gemm_desc* dp, void* stream) {
                 case 48: return launch_skinny<3>(d, s);
                 default: return launch_skinny<4>(d, s);
             }
-        case GK_BIG:
+        case GK_BIG: {
+            const int cv = g.big_cv(d.gn_stats != nullptr);     // gn_stats set: stats_ok was required above
             switch (g.bm * 1000 + g.bn) {
-                case 256320: return g.wgm == 4 ? launch_big<256, 320, 4, 4>(d, s, g.nsplit) : launch_big<256, 320, 2, 4>(d, s, g.nsplit);
-                case 128320: return g.wgm == 4 ? launch_big<128, 320, 4, 4>(d, s, g.nsplit) : launch_big<128, 320, 2, 4>(d, s, g.nsplit);
-                case 128160: return launch_big<128, 160, 4, 2>(d, s, g.nsplit);
-                case 256256: return launch_big<256, 256, 2, 4>(d, s, g.nsplit);
-                case 512128: return launch_big<512, 128, 8, 2>(d, s, g.nsplit);
-                default: return launch_big<256, 128, 4, 2>(d, s, g.nsplit);
+                case 256320: return g.wgm == 4 ? launch_big<256, 320, 4, 4>(d, s, g.nsplit, cv) : launch_big<256, 320, 2, 4>(d, s, g.nsplit, cv);
+                case 128320: return g.wgm == 4 ? launch_big<128, 320, 4, 4>(d, s, g.nsplit, cv) : launch_big<128, 320, 2, 4>(d, s, g.nsplit, cv);
+                case 128160: return launch_big<128, 160, 4, 2>(d, s, g.nsplit, cv);
+                case 256256: return launch_big<256, 256, 2, 4>(d, s, g.nsplit, cv);
+                case 512128: return launch_big<512, 128, 8, 2>(d, s, g.nsplit, cv);
+                default: return launch_big<256, 128, 4, 2>(d, s, g.nsplit, cv);
             }
+        }
         default:
             if (g.bm == 128 && g.bn == 128) return launch<128, 128>(d, s);
             if (g.bm == 128 && g.bn == 64) return launch<128, 64>(d, s);

@@ -1,6 +1,7 @@
-// Device-side building blocks shared by the GEMM translation units (gemm.hip: 4-wave BK=32 and 8/16-wave BK=64 kernels; gemm_mb.hip:
-// the multi-block-per-CU BK=32 kernels): measurement hooks, the zero page, direct-to-LDS loads, the three epilogues, the pinned
-// fragment schedule.  Everything here is static / inline: each translation unit gets its own copy (no relocatable device code).
+// Building blocks shared by the GEMM translation units (gemm.hip: the 4-wave BK = 32, the 8/16-wave BK = 64 and the skinny kernels; gemm_pp.hip:
+// the ping-pong kernels; gemm_halo.hip: the halo-staged convolution): measurement hooks, the decisions kernels and launchers must take alike, the
+// zero page, direct-to-LDS loads, the three epilogues, the pinned fragment schedule.  Everything here is static / inline: each translation unit
+// gets its own copy (no relocatable device code).
 #pragma once
 #include "common.h"
 #include <stdlib.h>
@@ -19,6 +20,21 @@ static inline const char* bench_env(const char* name) { return getenv(name); }
 #define FD_DBG_GE(p, v) false
 static inline const char* bench_env(const char*) { return nullptr; }
 #endif
+
+// Can this launch use the LDS-staged fp16 epilogue (gemm_epilogue_lds)?  ONE definition for the kernels (which epilogue runs, i.e. whether statistics
+// are written) and for gemm_plan on the host (whether a kernel can write gn_stats, i.e. whether Python allocates the buffer).  A macro, not a function:
+// as an inlined function the same expression compiled to different scalar compare sequences in conv_halo_kernel, and the hot kernels' ISA is held fixed.
+#define FD_GEMM_LDS_EPILOGUE_OK(p)                                                                                                  \
+    ((p).out_dtype == FD_OUT_F16 && ((p).N & 7) == 0 && ((p).ldc & 7) == 0 && (!(p).residual || ((p).ldr & 7) == 0) && \
+     (!(p).rowbias || ((p).ld_rowbias & 3) == 0))
+
+// n-tiles per band of the banded tile order (gemm_big_kernel): the band's B slab (gn * BN rows of ktot halfs, per split) should fit an XCD's L2 next to
+// the streaming A tiles
+constexpr long GEMM_L2_BUDGET = 3 * 1024 * 1024;
+static inline int gemm_band_ntiles(long l2_budget, int bn, long ktot, int ntn) {
+    const long gnl = l2_budget / ((long)bn * ktot * 2);
+    return (int)(gnl < 1 ? 1 : (gnl > ntn ? ntn : gnl));
+}
 
 struct ConvRow {
     int b, oy, ox;

@@ -165,32 +165,6 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(fd_gemm_desc p, int ntm,
                 auto issue = [&] {
                     issueB(c3, t3, nl);      // into the slot of step i - 1: every wave is past B_i, i.e. done with it
                     if constexpr (t < NAP) issueA(c + 1, tc);
-#ifdef HALO_GN_PROBE
-                    // MEASUREMENT ONLY (scratch/r06 probe; results are not meaningful): what would GroupNorm + SiLU applied to the staged A operand cost inside this
-                    // loop?  Chunk c + 1 has landed behind B_9c+5; during taps 6 .. 8 every thread takes its share of the buffer's 16-byte items through
-                    // LDS -> fp32 scale / shift (read from an LDS table) -> SiLU -> fp16 -> LDS, the arithmetic of gn_apply_kernel<silu>.
-                    if constexpr (t >= 6) {
-                        constexpr int NITEM = G::NPIECE * 64, PER = (NITEM + 511) / 512;
-                        constexpr int J0 = t == 6 ? 0 : (t == 7 ? (PER + 2) / 3 : 2 * ((PER + 2) / 3)), J1 = t == 6 ? (PER + 2) / 3 : (t == 7 ? 2 * ((PER + 2) / 3) : PER);
-                        f16* nb = abuf + ((c + 1) & 1) * G::ABUF;
-                        const float* tab = (const float*)(ring + PP_NST * HALO_BST);        // the dump groups stand in for the 32-channel (a, b) table
-#pragma unroll
-                        for (int j = J0; j < J1; ++j) {
-                            const int it = min(tid + 512 * j, NITEM - 1);      // branch-free (a divergent branch in the unrolled taps makes the allocator spill): the tail lanes redo the last item
-                            {
-                                f16x8 v = *(f16x8*)(nb + it * 8);
-#pragma unroll
-                                for (int h = 0; h < 2; ++h) {
-                                    const f32x4 sc = *(const f32x4*)(tab + (it & 3) * 16 + h * 4), sh = *(const f32x4*)(tab + (it & 3) * 16 + 8 + h * 4);
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[h * 4 + e] = (f16)silu_f((float)v[h * 4 + e] * sc[e] + sh[e]);
-                                    asm volatile("" : "+v"(v));
-                                }
-                                *(f16x8*)(nb + it * 8) = v;
-                            }
-                        }
-                    }
-#endif
                 };
                 if constexpr (LEAD) {
                     auto mid = [&] {
@@ -215,8 +189,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(fd_gemm_desc p, int ntm,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // drain the pad loads before the operand area is reused by the epilogue
     __syncthreads();
 
-    const bool lds_epi = p.out_dtype == FD_OUT_F16 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.residual || (p.ldr & 7) == 0) &&
-                         (!p.rowbias || (p.ld_rowbias & 3) == 0);
+    const bool lds_epi = FD_GEMM_LDS_EPILOGUE_OK(p);
     constexpr int TMC = BM == 256 ? TM / 2 : TM;
     static_assert(PP_NW * TMC * 16 * (WTN + 4) <= 2 * G::ABUF + PP_NST * HALO_BST, "epilogue staging does not fit the operand area");
     if (lds_epi) {
@@ -227,25 +200,23 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(fd_gemm_desc p, int ntm,
 #endif
 }
 
-template <int BM, int W, int CV, bool PRIO>
+// the s_setprio form only (policy bit 4 of gemm.hip is on in every build since round 3; fd_gemm_kernel_name prints it so)
+template <int BM, int W, int CV>
 static void launch_halo(const fd_gemm_desc& d, hipStream_t s, int ntm, int ntn, int gn) {
     static std::once_flag once;
     std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)conv_halo_kernel<BM, W, CV, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)halo_lds<BM, W>());
+        (void)hipFuncSetAttribute((const void*)conv_halo_kernel<BM, W, CV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)halo_lds<BM, W>());
     });
     constexpr size_t lds = halo_lds<BM, W>();
-    hipLaunchKernelGGL((conv_halo_kernel<BM, W, CV, PRIO>), dim3(ntm * ntn), dim3(512), lds, s, d, ntm, ntn, gn);
+    hipLaunchKernelGGL((conv_halo_kernel<BM, W, CV, true>), dim3(ntm * ntn), dim3(512), lds, s, d, ntm, ntn, gn);
 }
 
 template <int BM, int W>
-static void launch_halo_w(const fd_gemm_desc& d, hipStream_t s, bool prio) {
+static void launch_halo_w(const fd_gemm_desc& d, hipStream_t s) {
     const int ntm = d.M / BM, ntn = d.N / PP_BN;
-    const long l2_budget = 3 * 1024 * 1024;
-    long gnl = l2_budget / ((long)PP_BN * d.K * 2);
-    const int gn = (int)(gnl < 1 ? 1 : (gnl > ntn ? ntn : gnl));
-    (void)prio;      // the s_setprio form only (policy bit 4 of gemm.hip is on in every build since round 3)
-    if (d.gn_stats) launch_halo<BM, W, 3, true>(d, s, ntm, ntn, gn);
-    else launch_halo<BM, W, 1, true>(d, s, ntm, ntn, gn);
+    const int gn = gemm_band_ntiles(GEMM_L2_BUDGET, PP_BN, d.K, ntn);
+    if (d.gn_stats) launch_halo<BM, W, 3>(d, s, ntm, ntn, gn);
+    else launch_halo<BM, W, 1>(d, s, ntm, ntn, gn);
 }
 
 // stride-1 3x3 convolutions of square 16^2 / 32^2 / 64^2 maps whose tiles are whole image rows of one image, no split-K
@@ -255,19 +226,19 @@ bool fd_conv_halo_eligible(const fd_gemm_desc& d, int bm) {
     return (d.W * d.W) % bm == 0 && d.M % bm == 0 && (bm / 2) % d.W == 0 && (int64_t)d.N * d.ldb < (1LL << 31);
 }
 
-int fd_conv_halo_launch(const fd_gemm_desc& d, hipStream_t s, bool prio, int bm) {
+int fd_conv_halo_launch(const fd_gemm_desc& d, hipStream_t s, int bm) {
 #ifdef HALO_QUICK
-    launch_halo<HALO_QUICK, 64, 1, true>(d, s, 1, 1, 1);
+    launch_halo<HALO_QUICK, 64, 1>(d, s, 1, 1, 1);
     return 0;
 #else
     if (bm == 256) {
-        if (d.W == 64) launch_halo_w<256, 64>(d, s, prio);
-        else if (d.W == 32) launch_halo_w<256, 32>(d, s, prio);
-        else launch_halo_w<256, 16>(d, s, prio);
+        if (d.W == 64) launch_halo_w<256, 64>(d, s);
+        else if (d.W == 32) launch_halo_w<256, 32>(d, s);
+        else launch_halo_w<256, 16>(d, s);
     } else {
-        if (d.W == 64) launch_halo_w<128, 64>(d, s, prio);
-        else if (d.W == 32) launch_halo_w<128, 32>(d, s, prio);
-        else launch_halo_w<128, 16>(d, s, prio);
+        if (d.W == 64) launch_halo_w<128, 64>(d, s);
+        else if (d.W == 32) launch_halo_w<128, 32>(d, s);
+        else launch_halo_w<128, 16>(d, s);
     }
     return fd_check_launch("fd_gemm(conv halo)");
 #endif

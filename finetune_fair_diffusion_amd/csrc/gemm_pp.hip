@@ -274,8 +274,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(fd_gemm_desc p, int ntm, i
         return;
     }
 
-    const bool lds_epi = p.out_dtype == FD_OUT_F16 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.residual || (p.ldr & 7) == 0) &&
-                         (!p.rowbias || (p.ld_rowbias & 3) == 0);
+    const bool lds_epi = FD_GEMM_LDS_EPILOGUE_OK(p);
     constexpr int TMC = BM == 256 ? TM / 2 : TM;             // 8 waves x 64 rows x 84 halfs = 84 KB of staging per pass
     static_assert(PP_NW * TMC * 16 * (WTN + 4) <= PP_NST * STAGE, "epilogue staging does not fit the ring");
     if (p.act == FD_ACT_GEGLU) {
@@ -299,10 +298,7 @@ static void launch_pp(const fd_gemm_desc& d, hipStream_t s, int ntm, int ntn, in
 template <int BM>
 static void launch_pp_bm(const fd_gemm_desc& d, hipStream_t s, bool prio, int nsplit) {
     const int ntm = (d.M + BM - 1) / BM, ntn = d.N / PP_BN;
-    const long l2_budget = 3 * 1024 * 1024;
-    const long ktot = ((long)d.K + d.K2) / nsplit;
-    long gnl = l2_budget / ((long)PP_BN * ktot * 2);
-    const int gn = (int)(gnl < 1 ? 1 : (gnl > ntn ? ntn : gnl));
+    const int gn = gemm_band_ntiles(GEMM_L2_BUDGET, PP_BN, ((long)d.K + d.K2) / nsplit, ntn);
     if (d.gn_stats && nsplit == 1) {     // statistics-epilogue instantiations
         if (d.conv) { if (prio) launch_pp<BM, 3, true>(d, s, ntm, ntn, gn, 1); else launch_pp<BM, 3, false>(d, s, ntm, ntn, gn, 1); }
         else { if (prio) launch_pp<BM, 2, true>(d, s, ntm, ntn, gn, 1); else launch_pp<BM, 2, false>(d, s, ntm, ntn, gn, 1); }
@@ -322,7 +318,7 @@ bool fd_gemm_pp_eligible(const fd_gemm_desc& d) {
 
 // gemm_halo.hip: the same loop with the A operand of a stride-1 3x3 convolution staged once per channel chunk (round 6)
 bool fd_conv_halo_eligible(const fd_gemm_desc& d, int bm);
-int fd_conv_halo_launch(const fd_gemm_desc& d, hipStream_t s, bool prio, int bm);
+int fd_conv_halo_launch(const fd_gemm_desc& d, hipStream_t s, int bm);
 bool fd_conv_halo_takes(const fd_gemm_desc& d, int bm, int nsplit) {
 #ifdef FD_BENCH_HOOKS
     const char* e = getenv("FD_CONV_HALO");          // measurement build: FD_CONV_HALO=0 keeps the per-tap gather (re-read on every call for in-process A/Bs)
@@ -333,7 +329,7 @@ bool fd_conv_halo_takes(const fd_gemm_desc& d, int bm, int nsplit) {
 
 // bm: 256 or 128 rows per tile; nsplit > 1: split-K partials into d.workspace (the caller launches the reduction)
 int fd_gemm_launch_pp(const fd_gemm_desc& d, hipStream_t s, bool prio, int bm, int nsplit) {
-    if (fd_conv_halo_takes(d, bm, nsplit)) return fd_conv_halo_launch(d, s, prio, bm);
+    if (fd_conv_halo_takes(d, bm, nsplit)) return fd_conv_halo_launch(d, s, bm);      // (its s_setprio form only: ``prio`` does not reach it)
     if (bm == 256) launch_pp_bm<256>(d, s, prio, nsplit);
     else launch_pp_bm<128>(d, s, prio, nsplit);
     return fd_check_launch("fd_gemm(pp)");

@@ -1,5 +1,5 @@
-// Device pieces shared by the ping-pong GEMM kernels (gemm_pp.hip: one tile per workgroup; gemm_pps.hip: persistent workgroups that stream
-// tiles): counted vmcnt / raw barrier helpers, the pinned k = 32 fragment-streaming step with a mid-step hook, the staging geometry.
+// Device pieces shared by the ping-pong kernels (gemm_pp.hip: GEMM / per-tap 3x3 gather; gemm_halo.hip: the halo-staged 3x3 convolution):
+// counted vmcnt / raw barrier helpers, the pinned k = 32 fragment-streaming step with a mid-step hook, the staging geometry.
 #pragma once
 #include "gemm_device.h"
 
