@@ -126,6 +126,20 @@ __device__ __forceinline__ float act_grad(float z, int act) {
     }
 }
 
+// ---- bilinear resize of a cropped box (torchvision Resize on tensors: align_corners=False, no antialias), shared by fd_crop_resize_fwd / _bwd
+// (smallconv.hip) and fd_crop_resize_u8_fwd (evaluate.hip): the two source taps i0 <= i1 of output index o and the weight of i1
+__device__ __forceinline__ void bilinear_src(int o, int in_size, int out_size, int& i0, int& i1, float& lam) {
+    float src = ((float)o + 0.5f) * ((float)in_size / (float)out_size) - 0.5f;
+    if (src < 0.f) src = 0.f;
+    i0 = (int)src;
+    if (i0 > in_size - 1) i0 = in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    lam = src - (float)i0;
+}
+__device__ __forceinline__ float bilinear_blend(float ly, float lx, float v00, float v01, float v10, float v11) {
+    return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+}
+
 // ---- workgroup trace (measurement builds only, -DFD_BENCH_HOOKS): with a log buffer installed (fd_bench_wg_trace, runtime.hip) every workgroup of an
 // instrumented kernel appends (kernel id | waves << 8 | blockIdx.x << 16, XCC id << 32 | HW_ID, start, end) -- times on the 100 MHz s_memrealtime clock, which is
 // common to the whole chip -- so that scratch/wg_fill.py can say how many CUs held work at any moment of the SHIPPED multi-stream schedule (rocprofv3's kernel

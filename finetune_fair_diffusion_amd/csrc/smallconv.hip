@@ -390,14 +390,7 @@ extern "C" int fd_scale_channels_bwd(const void* x, const void* s, const void* d
 
 // ------------------------------------------------------------------ crop [x0,y0,x1,y1) + constant pad + bilinear resize to SxS
 // (torchvision Pad + Resize on tensors: align_corners=False, no antialias; 1-main-debias.py:267-290)
-__device__ __forceinline__ void bilinear_src(int o, int in_size, int out_size, int& i0, int& i1, float& lam) {
-    float src = ((float)o + 0.5f) * ((float)in_size / (float)out_size) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    lam = src - (float)i0;
-}
+// (bilinear_src / bilinear_blend: common.h, shared with the uint8 crop of evaluate.hip)
 // img [B,3,H,W] fp16 -> chips [B,3,S,S] fp16
 __global__ void crop_resize_fwd_kernel(const f16* img, const int32_t* boxes, float fill, f16* chips, int H, int W, int S, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -416,7 +409,7 @@ __global__ void crop_resize_fwd_kernel(const f16* img, const int32_t* boxes, flo
             const int yy = y0 + py, xx = x0 + px;
             return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? (float)ip[(int64_t)yy * W + xx] : fill;
         };
-        const float v = (1.f - ly) * ((1.f - lx) * at(ya, xa) + lx * at(ya, xb)) + ly * ((1.f - lx) * at(yb, xa) + lx * at(yb, xb));
+        const float v = bilinear_blend(ly, lx, at(ya, xa), at(ya, xb), at(yb, xa), at(yb, xb));
         chips[i] = (f16)v;
     }
 }

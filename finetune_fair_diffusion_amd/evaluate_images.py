@@ -1,0 +1,296 @@
+"""Offline evaluation of generated images -- the reference's ``eval-generated-images.py`` (:506-568 flags, :570-709 main) on the kernels of this
+package: the fourth step after train / export / generate.
+
+    python -m finetune_fair_diffusion_amd.evaluate_images --generated_imgs_dir out --save_dir out_results \\
+        --gender_classifier_weight g.pt --race_classifier_weight r.pt --age_classifier_weight a.pt
+
+reads ``generated_imgs_dir/prompt_{i}/img_{j}.jpg`` (what ``generate.py`` writes) in numeric order and writes into ``save_dir``
+
+  * ``test_results.pkl`` -- ``[face_indicators_all, face_bboxs_all, gender_logits_all, race_logits_all, age_logits_all]``, each a dict from prompt
+    index to a CPU tensor (bool [N], int64 [N,4], float32 [N,k]): the reference's file (:696-709);
+  * ``prompt_{i}.jpg`` -- the annotated grid of ``plot_in_grid_gender_race`` (:65-168; ``--grid gender_race_age``: ``plot_in_grid_gender_race_age``
+    :171-263, which the reference's main carries commented out), painted on the device in one launch and saved with ``quality=25``;
+  * ``metrics.json`` (build addition) -- per prompt and as a mean, exp-4's validation numbers (``evaluation.gap_metrics("exp-4", ...)``) of the three
+    test classifiers' softmax table, tallied on the device (``ops.eval_tally``): 32 integers per prompt are read back for it.
+
+Images are decoded on the host (PIL) by a small prefetch pool, uploaded as uint8 HWC and never converted as a whole: the face chips are cropped
+straight from the bytes (``ops.crop_resize_u8``: ``u/255*2-1`` in fp32 per tap, as the reference crops its fp32 tensor) and the grid is painted from
+the bytes with the reference's four fp32 roundings (``ops.eval_grid_attrs``).  An image without a face gets the all -1 chip and is classified like
+the others, as in the reference (:392, :643-645); only its indicator marks it.  The reference's aligned 112x112 chips are computed there but never
+saved: they are not built.  ``grid_attrs_host`` / ``grid_attrs_order`` are the plain host statements the grid kernel and the device ordering are
+tested against (tests/golden/reference_evalimages_grid.npz holds the reference's own arrays).
+"""
+import argparse
+import glob
+import json
+import math
+import os
+import pickle
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from .evaluation import BOX_WIDTH, FRAME, PALETTE_GENDER, PALETTE_RACE, STRIP, _json_safe, gap_metrics
+
+PALETTE_AGE = [(255, 255, 255), (255, 140, 0), (0, 100, 0)]          # white / darkorange / darkgreen (:219-224), index = pred + 1
+PALETTES = [PALETTE_GENDER, PALETTE_RACE, PALETTE_AGE]
+ATTR_K = (2, 4, 2)                   # gender, race, age: classes of the three test classifiers (:584, :591, :598)
+TABLE_ATTRS = [(0, 2), (2, 4), (6, 2)]
+DECODE_THREADS = 8                   # fixed: the pool only hides JPEG decoding behind the device work, it is not sized by the machine
+SYNTHETIC_SEEDS = (9101, 9102, 9103)
+
+
+def parse_args(input_args=None):
+    p = argparse.ArgumentParser(description="Script to evaluate generated images with the three test classifiers.")
+    a = p.add_argument
+    a("--gpu_id", type=int, default=0)
+    a("--gender_classifier_weight", type=str,
+      default="./data/5-trained-test-classifiers/CelebA-MobileNetLarge-Gender-09191318/epoch=19-step=25320_MobileNetLarge.pt")
+    a("--race_classifier_weight", type=str,
+      default="./data/5-trained-test-classifiers/fairface-MobileNetLarge-Race4-09191318/epoch=19-step=6760_MobileNetLarge.pt")
+    a("--age_classifier_weight", type=str,
+      default="./data/5-trained-test-classifiers/fairface-MobileNetLarge-Age2-09191319/epoch=19-step=6760_MobileNetLarge.pt")
+    a("--generated_imgs_dir", type=str,
+      default="./exp-3-debias-gender-race/outputs/from-paper_finetune-text-encoder_09190230/checkpoint-12200-generated-images/test_prompts_occupation")
+    a("--save_dir", type=str,
+      default="./exp-3-debias-gender-race/outputs/from-paper_finetune-text-encoder_09190230/checkpoint-12200-generated-images/test_prompts_occupation_results")
+    a("--batch_size", type=int, default=10, help="images per launch sequence (the reference evaluates one image at a time)")
+    a("--size_face", type=int, default=224)
+    a("--size_aligned_face", type=int, default=112, help="accepted for the reference's command lines; the aligned chips are not built")
+    a("--synthetic", action="store_true", default=False, help="(build addition) random classifier weights")
+    a("--face_provider", type=str, default="synthetic", help="(build addition) 'synthetic' or 'detector', as in train.py")
+    a("--grid", type=str, default="gender_race", choices=["gender_race", "gender_race_age", "off"],
+      help="(build addition) which of the reference's two grids to paint; its main runs gender_race")
+    return p.parse_args(input_args) if input_args is not None else p.parse_args()
+
+
+# ------------------------------------------------------------------------------------------ host statements
+def grid_attrs_shape(N, H, W, n_attr):
+    rows = int(math.sqrt(N))
+    cols = math.ceil(N / rows)
+    return rows, cols, (rows * (H + 2 * FRAME), cols * (W + STRIP * n_attr + 2 * FRAME), 3)
+
+
+def grid_attrs_order(preds, probs):
+    """Tile order of ``plot_in_grid_gender_race`` (:73-108; preds / probs [2, N]: gender, race) and ``plot_in_grid_gender_race_age`` (:176-187;
+    [3, N]: gender, race, age): gender 1 then 0, within it race 0..3 (within that age 0, 1), each group from the most to the least confident by the
+    RACE probability (two attributes) or the GENDER probability (three), then the rows with race -1 in index order.  Ties keep the index order (the
+    reference's ``argsort(descending=True)`` leaves them open).  A row in no group (gender -1 with a race) is shown nowhere in the reference and
+    refused here: the evaluator's predictions are never -1, and a -1 row of a caller is -1 in every attribute."""
+    preds, probs = np.asarray(preds), np.asarray(probs, dtype=np.float32)
+    n_attr, N = preds.shape
+    assert n_attr in (2, 3) and probs.shape == preds.shape
+    key = probs[1] if n_attr == 2 else probs[0]
+    out = []
+    for g in (1, 0):
+        for r in range(4):
+            for a in ((0, 1) if n_attr == 3 else (None,)):
+                m = (preds[0] == g) & (preds[1] == r)
+                if a is not None:
+                    m &= preds[2] == a
+                idx = np.nonzero(m)[0]
+                out += list(idx[np.argsort(-key[idx], kind="stable")])
+    out += list(np.nonzero(preds[1] == -1)[0])
+    assert sorted(out) == list(range(N)), "every image must fall in exactly one (gender, race[, age]) group or have race -1"
+    return np.asarray(out, dtype=np.int32)
+
+
+def grid_attrs_bar_rows(probs):
+    """Last row of each strip's white bar, -1 = no bar; probs [n_attr, N] fp32 (torch, any device) -> int32 [n_attr, N].  The reference draws
+    ``rectangle([(0,0),(50,(1-p)*512)])`` with p a Python float when ``p < 1``; in the three-strip grid the AGE bar's condition tests the RACE
+    probability (:232) while its height is age's."""
+    rows = ((1 - probs.double()) * 512).to(torch.int32)
+    cond = probs < 1
+    if probs.shape[0] == 3:
+        cond = torch.stack([cond[0], cond[1], cond[1]])
+    return torch.where(cond, rows, torch.full_like(rows, -1)).contiguous()
+
+
+def grid_attrs_host(images, order, boxes, preds, bar_rows, palettes):
+    """The numpy statement of ``fd_eval_grid_attrs_u8``: images [N,H,W,3] uint8, order [N] tile -> image, boxes [N,4] (x0,y0,x1,y1, both ends
+    drawn), preds / bar_rows [n_attr,N] (pred -1 = no face, bar_rows -1 = no bar), palettes [n_attr][(r,g,b)] indexed by pred + 1 -> uint8 grid.
+    Per tile, in the reference's drawing order: pixels ``trunc((((u/255)*2-1)*0.5+0.5)*255)`` in fp32; a 4-pixel BLACK outline of the box (PIL's rule,
+    ``evaluation.grid_host``), clipped to the image; then from the innermost (last) attribute outwards a 50-pixel strip of the class colour on the
+    left and its white bar over columns 0..50 of the image as expanded so far (one column of what lies to the right included) and rows
+    0..bar_rows; a 10-pixel black frame.  Tiles past N are white."""
+    images = np.asarray(images)
+    N, H, W, _ = images.shape
+    preds, bar_rows = np.asarray(preds), np.asarray(bar_rows)
+    n_attr = preds.shape[0]
+    rows, cols, shape = grid_attrs_shape(N, H, W, n_attr)
+    x = torch.from_numpy(images).float() / 255 * 2 - 1
+    pix = (x * 0.5 + 0.5).mul(255).to(torch.uint8).numpy()
+    th, tw = H + 2 * FRAME, W + STRIP * n_attr + 2 * FRAME
+    grid = np.full(shape, 255, dtype=np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for t in range(N):
+        i = int(order[t])
+        im = pix[i].copy()
+        x0, y0, x1, y1 = (int(v) for v in boxes[i])
+        hor = (((yy >= y0) & (yy < y0 + BOX_WIDTH)) | ((yy <= y1) & (yy > y1 - BOX_WIDTH))) & (xx >= x0) & (xx <= x1)
+        ya, yb = y0 + BOX_WIDTH, y1 - BOX_WIDTH + 1
+        lo, hi = (ya, yb - 1) if ya <= yb else (yb + 1, ya)
+        ver = (((xx >= x0) & (xx < x0 + BOX_WIDTH)) | ((xx <= x1) & (xx > x1 - BOX_WIDTH))) & (yy >= lo) & (yy <= hi)
+        im[hor | ver] = 0
+        for s in range(n_attr - 1, -1, -1):
+            wide = np.empty((H, im.shape[1] + STRIP, 3), dtype=np.uint8)
+            wide[:, :STRIP] = np.asarray(palettes[s][int(preds[s, i]) + 1], dtype=np.uint8)
+            wide[:, STRIP:] = im
+            if bar_rows[s, i] >= 0:
+                wide[:min(int(bar_rows[s, i]), H - 1) + 1, :STRIP + 1] = 255
+            im = wide
+        tile = np.zeros((th, tw, 3), dtype=np.uint8)
+        tile[FRAME:FRAME + H, FRAME:FRAME + im.shape[1]] = im
+        r, c = divmod(t, cols)
+        grid[r * th:(r + 1) * th, c * tw:(c + 1) * tw] = tile
+    return grid
+
+
+# ------------------------------------------------------------------------------------------ device side
+def _first_argmax(p):
+    """(first maximum's index, maximum) per row: a tie rule the device's ``max(dim).indices`` does not promise."""
+    mx = p.max(dim=-1).values
+    cols = torch.arange(p.shape[1], device=p.device).expand_as(p)
+    return torch.where(p == mx[:, None], cols, torch.full_like(cols, p.shape[1])).min(dim=-1).values, mx
+
+
+def device_order(preds, probs):
+    """``grid_attrs_order`` with torch on the tensors' device: two stable sorts (confidence, then group)."""
+    n_attr = preds.shape[0]
+    noface = preds[1] == -1
+    group = (1 - preds[0]) * 4 + preds[1]
+    if n_attr == 3:
+        group = group * 2 + preds[2]
+    group = torch.where(noface, torch.full_like(group, 64), group)
+    key = torch.where(noface, torch.zeros_like(probs[0]), probs[1] if n_attr == 2 else probs[0])
+    by_conf = torch.sort(-key, stable=True).indices
+    return by_conf[torch.sort(group[by_conf], stable=True).indices].to(torch.int32).contiguous()
+
+
+def device_grid(images, boxes, probs_list, which):
+    """The annotated grid (uint8 on the device) of one prompt: images [N,H,W,3] uint8, boxes [N,4] int32, probs_list = the three softmax tables
+    (gender, race, age) on the device.  Predictions, bars and the tile order are torch on the device; the painting is one launch."""
+    from . import ops
+    n_attr = 2 if which == "gender_race" else 3
+    pm = [_first_argmax(p) for p in probs_list[:n_attr]]
+    preds = torch.stack([a for a, _ in pm]).to(torch.int32).contiguous()
+    probs = torch.stack([m for _, m in pm]).float().contiguous()
+    P = max(len(p) for p in PALETTES[:n_attr])
+    pal = torch.tensor([p + [(255, 255, 255)] * (P - len(p)) for p in PALETTES[:n_attr]], dtype=torch.uint8, device=images.device)
+    return ops.eval_grid_attrs(images, device_order(preds, probs), boxes, preds, grid_attrs_bar_rows(probs), pal)
+
+
+def synthetic_classifier_state(which):
+    """``--synthetic``: seeded random weights of test classifier ``which`` (0 gender, 1 race, 2 age), representable in fp16."""
+    from . import weights as W
+    sd = W.synthetic_state_dict(W.mobilenet_param_shapes(ATTR_K[which]), seed=SYNTHETIC_SEEDS[which], gain=1.4)
+    return {k: (v.half().float() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def _numbered(paths, number):
+    return sorted(paths, key=number)
+
+
+def _decode(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def main(args, face_provider=None, log=print):
+    if not torch.cuda.is_available():
+        raise RuntimeError("finetune_fair_diffusion_amd.evaluate_images needs an MI355X (HIP device); there is no CPU path")
+    from PIL import Image
+    from . import ops
+    from .classifier import MobileNetV3Large
+    device = torch.device("cuda", args.gpu_id)
+    torch.cuda.set_device(device)
+    if face_provider is None:
+        if args.face_provider == "detector":
+            from .fairness import DetectorFaceProvider
+            face_provider = DetectorFaceProvider.from_installed()
+        elif args.face_provider == "synthetic":
+            from .fairness import SyntheticFaceProvider
+            face_provider = SyntheticFaceProvider()
+        else:
+            raise ValueError(f"--face_provider {args.face_provider}: 'synthetic' or 'detector'")
+    if args.batch_size < 1:
+        raise ValueError(f"--batch_size {args.batch_size}: at least 1")
+    classifiers = []
+    for which, path in enumerate((args.gender_classifier_weight, args.race_classifier_weight, args.age_classifier_weight)):
+        if args.synthetic:
+            sd = synthetic_classifier_state(which)
+        else:
+            from .pretrained import load_classifier
+            sd = load_classifier(path, ATTR_K[which])
+        classifiers.append(MobileNetV3Large(sd, device, ATTR_K[which]))
+
+    folders = _numbered(glob.glob(os.path.join(args.generated_imgs_dir, "prompt_*")), lambda x: int(x.split("_")[-1]))
+    os.makedirs(args.save_dir, exist_ok=True)
+    results = [{}, {}, {}, {}, {}]          # indicators, boxes, gender / race / age logits
+    metrics = {}
+    n_images, t0 = 0, time.time()
+    with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
+        for folder in folders:
+            prompt_idx = int(folder.split("_")[-1])
+            paths = _numbered(glob.glob(os.path.join(folder, "img_*.jpg")), lambda x: int(x.split("_")[-1].split(".")[0]))
+            if not paths:
+                continue
+            decoded = pool.map(_decode, paths)          # submitted now, consumed in order: decoding runs ahead of the device work
+            imgs_d, ind_p, boxes_p, logits_p = [], [], [], [[], [], []]
+            size = None
+            for b0 in range(0, len(paths), args.batch_size):
+                bp = paths[b0:b0 + args.batch_size]
+                batch = []
+                for path in bp:
+                    u = next(decoded)
+                    if size is None:
+                        size = u.shape
+                    if u.shape != size:
+                        raise ValueError(f"{path}: image of {u.shape[1]}x{u.shape[0]} in a prompt folder of {size[1]}x{size[0]} images "
+                                         "(the images of one prompt must share one size)")
+                    batch.append(u)
+                u8 = torch.from_numpy(np.stack(batch))                       # [b,H,W,3] uint8
+                u8_d = u8.to(device, non_blocking=False)
+                ind, boxes = face_provider(u8.permute(0, 3, 1, 2).float() / 255 * 2 - 1)      # what the reference hands get_face (:637-639)
+                ind = torch.as_tensor(ind, dtype=torch.bool).cpu()
+                boxes = torch.as_tensor(boxes).to("cpu", torch.int32)
+                boxes = torch.where(ind[:, None], boxes, torch.full_like(boxes, -1)).contiguous()
+                chips = ops.crop_resize_u8(u8_d, boxes.to(device), -1.0, args.size_face)
+                for k, clf in enumerate(classifiers):
+                    logits_p[k].append(clf(chips).float())
+                imgs_d.append(u8_d)
+                ind_p.append(ind)
+                boxes_p.append(boxes)
+            imgs_d = torch.cat(imgs_d)
+            ind, boxes = torch.cat(ind_p), torch.cat(boxes_p)
+            logits = [torch.cat(l) for l in logits_p]
+            probs = [torch.softmax(l, dim=-1) for l in logits]
+            table = torch.cat(probs, dim=1)
+            table = torch.where(ind.to(device)[:, None], table, torch.full_like(table, -1.0)).contiguous()
+            metrics[prompt_idx] = gap_metrics("exp-4", ops.eval_tally(table, TABLE_ATTRS).cpu())
+            if args.grid != "off":
+                grid = device_grid(imgs_d, boxes.to(device), probs, args.grid).cpu().numpy()
+                Image.fromarray(grid).save(os.path.join(args.save_dir, f"prompt_{prompt_idx}.jpg"), quality=25)
+            results[0][prompt_idx] = ind
+            results[1][prompt_idx] = boxes.to(torch.int64)
+            for k in range(3):
+                results[2 + k][prompt_idx] = logits[k].cpu()
+            n_images += len(paths)
+    with open(os.path.join(args.save_dir, "test_results.pkl"), "wb") as f:
+        pickle.dump(results, f)
+    keys = list(next(iter(metrics.values())).keys()) if metrics else []
+    out = {"per_prompt": {str(i): m for i, m in metrics.items()},
+           "mean": {k: float(np.array([m[k] for m in metrics.values()]).mean()) for k in keys}}
+    with open(os.path.join(args.save_dir, "metrics.json"), "w") as f:
+        json.dump(_json_safe(out), f, indent=1)
+    dt = time.time() - t0
+    if log is not None:
+        log(json.dumps({"evaluated_images": n_images, "prompts": len(metrics), "seconds": round(dt, 3), "images_per_s": round(n_images / dt, 2) if dt > 0 else None}))
+    return results, out
+
+
+if __name__ == "__main__":
+    main(parse_args())

@@ -823,6 +823,41 @@ def eval_grid(images, order, boxes, preds, maxprob, palette, rows=None, cols=Non
     return out
 
 
+# ----------------------------------------------------------------------------- offline evaluator (csrc/evaluate.hip; evaluate_images.py)
+def crop_resize_u8(img, boxes, fill, S):
+    """Face chips straight from decoded images (``fd_crop_resize_u8_fwd``): img [B,H,W,3] uint8 standing for ``u/255*2-1`` in fp32, boxes [B,4] int32
+    (x0,y0,x1,y1; an empty box gives a chip of ``fill``) -> chips [B,3,S,S] working dtype NCHW by the bilinear rule of ``crop_resize``."""
+    B, H, W, C = img.shape
+    assert img.dtype == torch.uint8 and C == 3 and img.is_contiguous(), (img.dtype, img.shape, img.stride())
+    assert boxes.dtype == torch.int32 and tuple(boxes.shape) == (B, 4) and boxes.is_contiguous(), (boxes.dtype, boxes.shape)
+    chips = torch.empty((B, 3, S, S), dtype=F16, device=img.device)
+    _call("fd_crop_resize_u8_fwd", _p(img), _p(boxes), fill, _p(chips), B, H, W, S, _stream())
+    return chips
+
+
+def eval_grid_attrs(images, order, boxes, preds, bar_rows, palette, rows=None, cols=None, out=None):
+    """The two- / three-strip grid of ``plot_in_grid_gender_race[_age]`` in one launch (``fd_eval_grid_attrs_u8``): images [N,H,W,3] uint8; order [N],
+    boxes [N,4], preds / bar_rows [n_attr,N] int32 (bar_rows -1 = no bar); palette [n_attr, <= 6, 3] uint8 (pred -1, 0, 1, ...), all on the device
+    -> [rows*(H+20), cols*(W+50*n_attr+20), 3] uint8."""
+    N, H, W, C = images.shape
+    n_attr = preds.shape[0]
+    assert images.dtype == torch.uint8 and C == 3 and images.is_contiguous(), (images.dtype, images.shape, images.stride())
+    rows = int(math.sqrt(N)) if rows is None else rows
+    cols = math.ceil(N / rows) if cols is None else cols
+    pal = torch.full((max(n_attr, 1), 6, 3), 255, dtype=torch.uint8, device=images.device)
+    assert palette.dtype == torch.uint8 and palette.dim() == 3 and palette.shape[0] == n_attr and palette.shape[2] == 3, (palette.dtype, palette.shape)
+    pal[:, :palette.shape[1]] = palette
+    for t, shp in ((order, (N,)), (boxes, (N, 4)), (preds, (n_attr, N)), (bar_rows, (n_attr, N))):
+        assert t.dtype == torch.int32 and tuple(t.shape) == shp and t.is_contiguous(), (t.dtype, t.shape, shp)
+    shape = (rows * (H + 20), cols * (W + 50 * n_attr + 20), 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=images.device)
+    # the entry point cannot see the size of the buffer it fills
+    assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape, (out.dtype, out.shape, shape)
+    _call("fd_eval_grid_attrs_u8", _p(images), _p(order), _p(boxes), _p(preds), _p(bar_rows), _p(pal), _p(out), N, H, W, n_attr, rows, cols, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- text-encoder attention
 def small_attn_fwd(q, k, v, key_valid, B, H, T, d, scale, causal=True, save_p=False):
     o = torch.empty_like(q)

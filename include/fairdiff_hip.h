@@ -361,6 +361,23 @@ int fd_eval_tally(const float* probs, int N, int ld, const int32_t* attr_c0, con
 int fd_eval_grid_u8(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const float* maxprob, const uint8_t* palette,
                     uint8_t* grid, int N, int H, int W, int rows, int cols, void* stream);
 
+
+/* ---- offline evaluation of generated images (evaluate_images.py; eval-generated-images.py).  Both entry points read JPEG-decoded uint8 HWC images,
+ * a pixel u standing for ((float)u / 255) * 2 - 1 in fp32 (a true division; each operation rounded once).  Additive: FD_ABI_VERSION is unchanged.
+ * crop_face (:296-319): crop boxes[b] = x0,y0,x1,y1 (x1, y1 exclusive; may exceed the image -> fill) of img [B,H,W,3] uint8 and resize it bilinearly
+ * (align_corners=False, no antialias: the taps and weights of fd_crop_resize_fwd) to chips [B,3,S,S] working dtype NCHW, rounded once at the store.
+ * A box with x1 <= x0 or y1 <= y0 (the no-face box -1,-1,-1,-1) gives a chip of ``fill``.  B >= 1; S, H, W 1..4096. */
+int fd_crop_resize_u8_fwd(const uint8_t* img, const int32_t* boxes, float fill, void* chips, int B, int H, int W, int S, void* stream);
+/* The whole grid of plot_in_grid_gender_race (:65-168; n_attr = 2) / plot_in_grid_gender_race_age (:171-263; n_attr = 3) in one launch: images
+ * [N,H,W,3] uint8 -> grid [rows*(H+20), cols*(W+50*n_attr+20), 3] uint8 (4-byte aligned).  Tile i shows image order[i]: pixels
+ * trunc((((u/255)*2-1)*0.5+0.5)*255) (four fp32 roundings); the outline of boxes[order[i]] = x0,y0,x1,y1 (both ends drawn, 4 pixels wide, PIL's rule)
+ * in BLACK; attribute s = 0 .. n_attr-1 from the outside in: a 50-pixel strip over inner columns [50s, 50s+50) in palette[s][preds[s][i]+1] and, when
+ * bar_rows[s][i] >= 0, a white bar over inner columns 50s..50s+50 INCLUSIVE and rows 0..bar_rows[s][i] (clipped to the tile), outer strips winning;
+ * a 10-pixel black frame.  Tiles past N are white; the index text is not drawn.  order [N], boxes [N,4], preds / bar_rows [n_attr,N] int32, palette
+ * [n_attr,FD_EVAL_PALETTE,3] uint8, all on the device.  n_attr 1..3; rows*cols holds N tiles with at most the last row partly filled; N, H, W 1..4096. */
+int fd_eval_grid_attrs_u8(const uint8_t* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
+                          const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
