@@ -10,7 +10,12 @@ cannot be set from YAML and booleans follow Python's ``bool(value)`` -- plus the
   --num_classifier_logits  80 (exp-1) / 6 (exp-3,5,6) / 8 (exp-4)
   --lora_up_std          std of the LoRA ``up`` init; 0 (default) = zeros like the reference, non-zero only for synthetic experiments
   --validation           off (default) / metrics / grids: the reference's ``evaluation_step`` at step 0 and every ``--evaluate_every_n_iter`` steps
-                         (evaluation.py); "off" leaves the run -- JSON lines, random streams, checkpoints -- exactly as without the flag
+                         (evaluation.py); "off" leaves the run -- JSON lines, random streams, checkpoints -- exactly as without the flag;
+                         grids_attrs: as grids, with one strip per attribute in the grids of exp-3/4/5 (the reference's own validation grids)
+  --train_monitor        off (default) / metrics / plots: what the reference's loop logs about every training batch.  metrics: the step's JSON line
+                         gains ``train_<gap metric>`` of the gathered batch, ``num_faces`` and ``num_faces_total``; plots: also, every
+                         ``--train_plot_every_n_iter`` steps of an epoch, ``<output_dir>/imgs/train-{global_step}_{generated|ori}.jpg``.  "off"
+                         leaves the run exactly as without the flag; no mode draws a random number or changes a result of the step
 
 The multi-attribute experiments change a few flags and defaults (exp-3-debias-gender-race/1-main-debias.py:343-660,
 exp-4-debias-gender-race-age/...:343-672, exp-5-...:343-690; exp-2-debias-gender-token/...:453-780 drops the two LoRA switches and adds
@@ -129,7 +134,8 @@ def build_parser(experiment="exp-1"):
     return p
 
 
-EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="synthetic", num_classifier_logits=80, lora_up_std=0.0, validation="off")
+EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="synthetic", num_classifier_logits=80, lora_up_std=0.0, validation="off",
+                      train_monitor="off")
 
 
 def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
@@ -140,7 +146,8 @@ def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
         p.add_argument("--face_provider", type=str, default="synthetic")
         p.add_argument("--num_classifier_logits", type=int, default=80)
         p.add_argument("--lora_up_std", type=float, default=0.0)
-        p.add_argument("--validation", type=str, default="off", choices=["off", "metrics", "grids"])
+        p.add_argument("--validation", type=str, default="off", choices=["off", "metrics", "grids", "grids_attrs"])
+        p.add_argument("--train_monitor", type=str, default="off", choices=["off", "metrics", "plots"])
     args = p.parse_args(input_args) if input_args is not None else p.parse_args()
     if args.config:
         with open(args.config, "r") as f:

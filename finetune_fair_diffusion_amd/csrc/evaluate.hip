@@ -3,6 +3,9 @@
 // only 32 integers and the finished grid cross to the host.  Neither kernel is on the training step's critical path.
 // The offline evaluator (evaluate_images.py; eval-generated-images.py) adds the two kernels that start from JPEG-decoded uint8 HWC images: the face-chip
 // crop (crop_face :296-319 on ``u/255*2-1``) and the two- / three-strip grid (plot_in_grid_gender_race :65-168, plot_in_grid_gender_race_age :171-263).
+// The training monitor (step.py; exp-3 1-main-debias.py :1989-2002, :2063-2075, exp-4 :2088, :2176) paints the same two- / three-strip grid from the
+// working-dtype NCHW images the step holds.  The three painters share one tile geometry, outline, strip / bar rule, pixel rule and thread mapping
+// (the helpers below); they differ in the pixel fetch, and the one-strip painter in the colour of its outline and the form its bar arrives in.
 #include "common.h"
 #include "../../include/fairdiff_hip.h"
 
@@ -73,7 +76,7 @@ extern "C" int fd_eval_tally(const float* probs, int N, int ld, const int32_t* a
     return fd_check_launch("fd_eval_tally");
 }
 
-// ---------------------------------------------------------------- fd_eval_grid_u8
+// ---------------------------------------------------------------- the grid painters: shared device helpers
 #define EG_STRIP 50
 #define EG_FRAME 10
 #define EG_BOX 4
@@ -87,80 +90,57 @@ __device__ __forceinline__ bool eval_box_outline(int x, int y, int x0, int y0, i
     return hor || ver;
 }
 
-// one output byte of the grid; ``idx`` = flat byte index into [rows*(H+20), cols*(W+70), 3]
-__device__ __forceinline__ uint32_t eval_grid_byte(int64_t idx, const f16* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
-                                                   const int32_t* __restrict__ preds, const float* __restrict__ maxprob, const uint8_t* __restrict__ palette,
-                                                   int N, int H, int W, int cols) {
-    const int tw = W + EG_STRIP + 2 * EG_FRAME, th = H + 2 * EG_FRAME;
-    const int c = (int)(idx % 3);
+// Tile geometry of a grid [rows*(H+20), cols*(W+50*n_strip+20), 3] at flat byte index ``idx``.  Returns the byte of what lies outside a tile's inner
+// area -- 255 for a tile past N (white) or one whose order entry is malformed (it reads nothing), 0 for the 10-pixel black frame -- or -1 with
+// ``p`` = the channel, the image shown and the position inside the strip-expanded image.
+struct EvalTilePos {
+    int c, i, ix, iy;
+};
+__device__ __forceinline__ int eval_tile_locate(int64_t idx, const int32_t* __restrict__ order, int N, int H, int W, int n_strip, int cols, EvalTilePos& p) {
+    const int tw = W + EG_STRIP * n_strip + 2 * EG_FRAME, th = H + 2 * EG_FRAME;
+    p.c = (int)(idx % 3);
     const int64_t pxl = idx / 3;
     const int GW = cols * tw;
     const int X = (int)(pxl % GW), Y = (int)(pxl / GW);
     const int tc = X / tw, tx = X - tc * tw, tr = Y / th, ty = Y - tr * th;
     const int t = tr * cols + tc;
-    if (t >= N) return 255u;                                                                     // tiles past N are white
-    if (tx < EG_FRAME || tx >= tw - EG_FRAME || ty < EG_FRAME || ty >= th - EG_FRAME) return 0u;  // black frame
-    const int ix = tx - EG_FRAME, iy = ty - EG_FRAME;
-    const int i = order[t];
-    if (i < 0 || i >= N) return 255u;                                                            // a malformed order entry reads nothing
-    const float p = maxprob[i];
-    // the white bar covers columns 0..50 of the strip-expanded image (the image's first column included) and rows 0..int((1-p)*512), computed in
-    // double from the fp32 value as the reference does with ``.item()``
-    if (p < 1.f && ix <= EG_STRIP && iy <= (int)((1.0 - (double)p) * 512.0)) return 255u;
-    const int cls = min(max(preds[i], -1), FD_EVAL_PALETTE - 2);
-    const uint32_t col = palette[(cls + 1) * 3 + c];
-    if (ix < EG_STRIP) return col;
-    const int x = ix - EG_STRIP, y = iy;
-    const int x0 = boxes[4 * i], y0 = boxes[4 * i + 1], x1 = boxes[4 * i + 2], y1 = boxes[4 * i + 3];
-    if (eval_box_outline(x, y, x0, y0, x1, y1)) return col;
+    if (t >= N) return 255;
+    if (tx < EG_FRAME || tx >= tw - EG_FRAME || ty < EG_FRAME || ty >= th - EG_FRAME) return 0;
+    p.ix = tx - EG_FRAME;
+    p.iy = ty - EG_FRAME;
+    p.i = order[t];
+    if (p.i < 0 || p.i >= N) return 255;
+    return -1;
+}
+
+// Strip s (counted from the outside in) at position (ix, iy) of the strip-expanded image; ``bar`` = last row of its white bar, -1 = no bar.  The bar is
+// 51 columns wide -- one column into whatever lies to its right: the next strip's colour or, for the last strip, the image's first column -- and an
+// outer strip is drawn later in the reference, so the caller asks the strips in the order s = 0, 1, ... and the first answer other than EG_RIGHT wins.
+enum { EG_RIGHT = 0, EG_BAR = 1, EG_COLOUR = 2 };
+__device__ __forceinline__ int eval_strip(int ix, int iy, int s, int bar) {
+    if (bar >= 0 && ix >= EG_STRIP * s && ix <= EG_STRIP * s + EG_STRIP && iy <= bar) return EG_BAR;
+    return ix < EG_STRIP * s + EG_STRIP ? EG_COLOUR : EG_RIGHT;
+}
+
+__device__ __forceinline__ uint32_t eval_palette(const uint8_t* __restrict__ palette, int s, int pred, int c) {
+    const int cls = min(max(pred, -1), FD_EVAL_PALETTE - 2);
+    return palette[(s * FD_EVAL_PALETTE + cls + 1) * 3 + c];
+}
+
+// ``ToPILImage()(x*0.5+0.5)`` (generate.to_uint8_hwc): the sum and the product in fp32, each rounded once (no x * 127.5 + 127.5; x * 0.5 is exact),
+// then truncation.  Images are in [-1,1] by contract; a value outside must not make the conversion undefined.
+__device__ __forceinline__ uint32_t eval_pixel_byte(float x) {
     float v;
     {
-        // generate.to_uint8_hwc: (x * 0.5 + 0.5) in fp32, then * 255, then truncation -- the sum and the product must each round once (no
-        // x * 127.5 + 127.5).  The compiler may still fuse x * 0.5 + 0.5 into one fma: x * 0.5 is exact for a 16-bit input, so the result is the same
 #pragma clang fp reassociate(off) contract(off)
-        const float u = (float)img[(((int64_t)i * 3 + c) * H + y) * W + x] * 0.5f + 0.5f;
+        const float h = x * 0.5f;
+        const float u = h + 0.5f;
         v = u * 255.f;
     }
-    v = fminf(fmaxf(v, 0.f), 255.f);      // images are in [-1,1] by contract; a value outside must not make the conversion undefined
+    v = fminf(fmaxf(v, 0.f), 255.f);
     return (uint32_t)(int)v;
 }
 
-__global__ __launch_bounds__(256) void eval_grid_kernel(const f16* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
-                                                        const int32_t* __restrict__ preds, const float* __restrict__ maxprob, const uint8_t* __restrict__ palette,
-                                                        uint8_t* __restrict__ grid, int N, int H, int W, int cols, int64_t total) {
-    // each thread produces 4 consecutive bytes and writes them with one 32-bit store (the buffer start is 4-byte aligned, checked by the entry point);
-    // the last 1..3 bytes of a grid whose size is not a multiple of 4 are written one by one
-    const int64_t nquad = (total + 3) / 4;
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = q * 4;
-        if (b + 4 <= total) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w |= eval_grid_byte(b + j, img, order, boxes, preds, maxprob, palette, N, H, W, cols) << (8 * j);
-            *reinterpret_cast<uint32_t*>(grid + b) = w;
-        } else {
-            for (int64_t k = b; k < total; ++k) grid[k] = (uint8_t)eval_grid_byte(k, img, order, boxes, preds, maxprob, palette, N, H, W, cols);
-        }
-    }
-}
-
-extern "C" int fd_eval_grid_u8(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const float* maxprob, const uint8_t* palette,
-                               uint8_t* grid, int N, int H, int W, int rows, int cols, void* stream) {
-    FD_REQUIRE(images && order && boxes && preds && maxprob && palette && grid, "fd_eval_grid_u8: null pointer");
-    FD_REQUIRE(N >= 1 && N <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "fd_eval_grid_u8: N = %d, H = %d, W = %d, supported 1..4096 each", N, H, W);
-    FD_REQUIRE(rows >= 1 && cols >= 1 && (int64_t)rows * cols >= N && (int64_t)rows * cols < (int64_t)N + cols,
-               "fd_eval_grid_u8: a %d x %d grid does not hold %d tiles with a partly filled last row at most", rows, cols, N);
-    FD_REQUIRE(((uintptr_t)grid & 3) == 0, "fd_eval_grid_u8: the grid buffer must be 4-byte aligned");
-    const int64_t total = (int64_t)rows * (H + 2 * EG_FRAME) * cols * (W + EG_STRIP + 2 * EG_FRAME) * 3;
-    FD_REQUIRE(total < ((int64_t)1 << 40), "fd_eval_grid_u8: a grid of %lld bytes is not supported", (long long)total);
-    const int64_t nquad = (total + 3) / 4;
-    const int64_t blocks = (nquad + 255) / 256;
-    hipLaunchKernelGGL(eval_grid_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, (const f16*)images, order, boxes, preds,
-                       maxprob, palette, grid, N, H, W, cols, total);
-    return fd_check_launch("fd_eval_grid_u8");
-}
-
-// ---------------------------------------------------------------- uint8 images of the offline evaluator
 // ``img.float()/255*2-1`` (eval-generated-images.py:637) as torch computes it in fp32: a true division, then a product and a difference, each rounded
 // once.  The translation unit is built with -ffast-math, under which an fp32 ``u / 255.f`` is lowered to u * (1/255) whatever ``#pragma clang fp``
 // says (the approximate-function flag has no pragma), and that product differs from the quotient in the last bit for part of the 256 values.  The
@@ -172,6 +152,80 @@ __device__ __forceinline__ float eval_u8_unit(uint32_t u) {
     const float d = (float)((double)u / 255.0);
     const float t = d * 2.f;
     return t - 1.f;
+}
+
+
+// The pixel fetch, the one thing the painters do not share: channel c of pixel (x, y) of image i as the fp32 value the reference's tensor holds there.
+// Working dtype NCHW: the stored value.  uint8 HWC: ``u/255*2-1``, so that the painted byte carries four fp32 roundings (quotient, difference, sum,
+// product) and 63 of the 256 byte values come out one lower than they went in.
+__device__ __forceinline__ float eval_fetch(const f16* __restrict__ img, int i, int c, int y, int x, int H, int W) {
+    return (float)img[(((int64_t)i * 3 + c) * H + y) * W + x];
+}
+__device__ __forceinline__ float eval_fetch(const uint8_t* __restrict__ img, int i, int c, int y, int x, int H, int W) {
+    return eval_u8_unit(img[(((int64_t)i * H + y) * W + x) * 3 + c]);
+}
+
+// Thread mapping of the painters: each thread produces 4 consecutive bytes and writes them with one 32-bit store (the buffer start is 4-byte aligned,
+// checked by the entry points); the last 1..3 bytes of a grid whose size is not a multiple of 4 are written one by one.
+template <typename ByteFn>
+__device__ __forceinline__ void eval_grid_store(uint8_t* __restrict__ grid, int64_t total, ByteFn byte) {
+    const int64_t nquad = (total + 3) / 4;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = q * 4;
+        if (b + 4 <= total) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w |= byte(b + j) << (8 * j);
+            *reinterpret_cast<uint32_t*>(grid + b) = w;
+        } else {
+            for (int64_t k = b; k < total; ++k) grid[k] = (uint8_t)byte(k);
+        }
+    }
+}
+
+static unsigned eval_grid_blocks(int64_t total) {
+    const int64_t blocks = ((total + 3) / 4 + 255) / 256;
+    return (unsigned)(blocks < 65536 ? blocks : 65536);
+}
+
+// ---------------------------------------------------------------- fd_eval_grid_u8
+// one output byte of the grid; ``idx`` = flat byte index into [rows*(H+20), cols*(W+70), 3]
+__device__ __forceinline__ uint32_t eval_grid_byte(int64_t idx, const f16* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
+                                                   const int32_t* __restrict__ preds, const float* __restrict__ maxprob, const uint8_t* __restrict__ palette,
+                                                   int N, int H, int W, int cols) {
+    EvalTilePos p;
+    const int outside = eval_tile_locate(idx, order, N, H, W, 1, cols, p);
+    if (outside >= 0) return (uint32_t)outside;
+    const int i = p.i;
+    // the white bar ends at row int((1-p)*512), computed in double from the fp32 value as the reference does with ``.item()``
+    const float pr = maxprob[i];
+    const int hit = eval_strip(p.ix, p.iy, 0, pr < 1.f ? (int)((1.0 - (double)pr) * 512.0) : -1);
+    if (hit == EG_BAR) return 255u;
+    const uint32_t col = eval_palette(palette, 0, preds[i], p.c);
+    if (hit == EG_COLOUR) return col;
+    const int x = p.ix - EG_STRIP, y = p.iy;
+    if (eval_box_outline(x, y, boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3])) return col;      // the outline has the class colour here
+    return eval_pixel_byte(eval_fetch(img, i, p.c, y, x, H, W));
+}
+
+__global__ __launch_bounds__(256) void eval_grid_kernel(const f16* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
+                                                        const int32_t* __restrict__ preds, const float* __restrict__ maxprob, const uint8_t* __restrict__ palette,
+                                                        uint8_t* __restrict__ grid, int N, int H, int W, int cols, int64_t total) {
+    eval_grid_store(grid, total, [=](int64_t k) { return eval_grid_byte(k, img, order, boxes, preds, maxprob, palette, N, H, W, cols); });
+}
+
+extern "C" int fd_eval_grid_u8(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const float* maxprob, const uint8_t* palette,
+                               uint8_t* grid, int N, int H, int W, int rows, int cols, void* stream) {
+    FD_REQUIRE(images && order && boxes && preds && maxprob && palette && grid, "fd_eval_grid_u8: null pointer");
+    FD_REQUIRE(N >= 1 && N <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "fd_eval_grid_u8: N = %d, H = %d, W = %d, supported 1..4096 each", N, H, W);
+    FD_REQUIRE(rows >= 1 && cols >= 1 && (int64_t)rows * cols >= N && (int64_t)rows * cols < (int64_t)N + cols,
+               "fd_eval_grid_u8: a %d x %d grid does not hold %d tiles with a partly filled last row at most", rows, cols, N);
+    FD_REQUIRE(((uintptr_t)grid & 3) == 0, "fd_eval_grid_u8: the grid buffer must be 4-byte aligned");
+    const int64_t total = (int64_t)rows * (H + 2 * EG_FRAME) * cols * (W + EG_STRIP + 2 * EG_FRAME) * 3;
+    FD_REQUIRE(total < ((int64_t)1 << 40), "fd_eval_grid_u8: a grid of %lld bytes is not supported", (long long)total);
+    hipLaunchKernelGGL(eval_grid_kernel, dim3(eval_grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const f16*)images, order, boxes, preds, maxprob, palette,
+                       grid, N, H, W, cols, total);
+    return fd_check_launch("fd_eval_grid_u8");
 }
 
 // ---------------------------------------------------------------- fd_crop_resize_u8_fwd
@@ -222,80 +276,58 @@ extern "C" int fd_crop_resize_u8_fwd(const uint8_t* img, const int32_t* boxes, f
     return fd_check_launch("fd_crop_resize_u8_fwd");
 }
 
-// ---------------------------------------------------------------- fd_eval_grid_attrs_u8
+// ---------------------------------------------------------------- fd_eval_grid_attrs_u8, fd_eval_grid_attrs
 // one output byte of the grid; ``idx`` = flat byte index into [rows*(H+20), cols*(W+50*n_attr+20), 3].  The rules (which strip, which bar) are the
-// caller's: the kernel paints preds / bar_rows / palette as given.
-__device__ __forceinline__ uint32_t eval_grid_attrs_byte(int64_t idx, const uint8_t* __restrict__ img, const int32_t* __restrict__ order,
+// caller's: the kernel paints preds / bar_rows / palette as given.  T = uint8_t: HWC bytes of the offline evaluator; T = f16: the training step's NCHW images.
+template <typename T>
+__device__ __forceinline__ uint32_t eval_grid_attrs_byte(int64_t idx, const T* __restrict__ img, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ boxes, const int32_t* __restrict__ preds, const int32_t* __restrict__ bar_rows,
                                                          const uint8_t* __restrict__ palette, int N, int H, int W, int n_attr, int cols) {
-    const int tw = W + EG_STRIP * n_attr + 2 * EG_FRAME, th = H + 2 * EG_FRAME;
-    const int c = (int)(idx % 3);
-    const int64_t pxl = idx / 3;
-    const int GW = cols * tw;
-    const int X = (int)(pxl % GW), Y = (int)(pxl / GW);
-    const int tc = X / tw, tx = X - tc * tw, tr = Y / th, ty = Y - tr * th;
-    const int t = tr * cols + tc;
-    if (t >= N) return 255u;                                                                     // tiles past N are white
-    if (tx < EG_FRAME || tx >= tw - EG_FRAME || ty < EG_FRAME || ty >= th - EG_FRAME) return 0u;  // black frame
-    const int ix = tx - EG_FRAME, iy = ty - EG_FRAME;
-    const int i = order[t];
-    if (i < 0 || i >= N) return 255u;                                                            // a malformed order entry reads nothing
-    // strips from the outside in: an outer strip is drawn later in the reference, so its bar -- 51 columns wide, one column into whatever lies to its
-    // right -- wins over the next strip's colour (or, for the last strip, over the image's first column)
+    EvalTilePos p;
+    const int outside = eval_tile_locate(idx, order, N, H, W, n_attr, cols, p);
+    if (outside >= 0) return (uint32_t)outside;
+    const int i = p.i;
     for (int s = 0; s < n_attr; ++s) {
-        const int bar = bar_rows[(int64_t)s * N + i];
-        if (bar >= 0 && ix >= EG_STRIP * s && ix <= EG_STRIP * s + EG_STRIP && iy <= bar) return 255u;
-        if (ix < EG_STRIP * s + EG_STRIP) {
-            const int cls = min(max(preds[(int64_t)s * N + i], -1), FD_EVAL_PALETTE - 2);
-            return palette[(s * FD_EVAL_PALETTE + cls + 1) * 3 + c];
-        }
+        const int hit = eval_strip(p.ix, p.iy, s, bar_rows[(int64_t)s * N + i]);
+        if (hit == EG_BAR) return 255u;
+        if (hit == EG_COLOUR) return eval_palette(palette, s, preds[(int64_t)s * N + i], p.c);
     }
-    const int x = ix - EG_STRIP * n_attr, y = iy;
+    const int x = p.ix - EG_STRIP * n_attr, y = p.iy;
     if (eval_box_outline(x, y, boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3])) return 0u;      // the outline is black here
-    float v;
-    {
-        // ``ToPILImage()(img*0.5+0.5)`` on img = u/255*2-1: four fp32 roundings (quotient, difference, sum, product; the factors 2 and 0.5 are exact),
-        // then truncation -- 63 of the 256 byte values come out one lower than they went in
-#pragma clang fp reassociate(off) contract(off)
-        const float h = eval_u8_unit(img[(((int64_t)i * H + y) * W + x) * 3 + c]) * 0.5f;
-        const float w = h + 0.5f;
-        v = w * 255.f;
-    }
-    return (uint32_t)(int)v;      // in [0, 255] for every byte value
+    return eval_pixel_byte(eval_fetch(img, i, p.c, y, x, H, W));
 }
 
-__global__ __launch_bounds__(256) void eval_grid_attrs_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
+template <typename T>
+__global__ __launch_bounds__(256) void eval_grid_attrs_kernel(const T* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
                                                               const int32_t* __restrict__ preds, const int32_t* __restrict__ bar_rows,
                                                               const uint8_t* __restrict__ palette, uint8_t* __restrict__ grid, int N, int H, int W, int n_attr, int cols,
                                                               int64_t total) {
-    // 4 consecutive bytes per thread and one 32-bit store, the last 1..3 bytes one by one: as eval_grid_kernel
-    const int64_t nquad = (total + 3) / 4;
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = q * 4;
-        if (b + 4 <= total) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w |= eval_grid_attrs_byte(b + j, img, order, boxes, preds, bar_rows, palette, N, H, W, n_attr, cols) << (8 * j);
-            *reinterpret_cast<uint32_t*>(grid + b) = w;
-        } else {
-            for (int64_t k = b; k < total; ++k) grid[k] = (uint8_t)eval_grid_attrs_byte(k, img, order, boxes, preds, bar_rows, palette, N, H, W, n_attr, cols);
-        }
-    }
+    eval_grid_store(grid, total, [=](int64_t k) { return eval_grid_attrs_byte(k, img, order, boxes, preds, bar_rows, palette, N, H, W, n_attr, cols); });
+}
+
+// the two entry points: one argument list, one set of refusals
+template <typename T>
+static int eval_grid_attrs_launch(const char* who, const T* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
+                                  const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream) {
+    FD_REQUIRE(images && order && boxes && preds && bar_rows && palette && grid, "%s: null pointer", who);
+    FD_REQUIRE(N >= 1 && N <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "%s: N = %d, H = %d, W = %d, supported 1..4096 each", who, N, H, W);
+    FD_REQUIRE(n_attr >= 1 && n_attr <= FD_EVAL_MAX_ATTR, "%s: n_attr = %d, supported 1..%d", who, n_attr, FD_EVAL_MAX_ATTR);
+    FD_REQUIRE(rows >= 1 && cols >= 1 && (int64_t)rows * cols >= N && (int64_t)rows * cols < (int64_t)N + cols,
+               "%s: a %d x %d grid does not hold %d tiles with a partly filled last row at most", who, rows, cols, N);
+    FD_REQUIRE(((uintptr_t)grid & 3) == 0, "%s: the grid buffer must be 4-byte aligned", who);
+    const int64_t total = (int64_t)rows * (H + 2 * EG_FRAME) * cols * (W + EG_STRIP * n_attr + 2 * EG_FRAME) * 3;
+    FD_REQUIRE(total < ((int64_t)1 << 40), "%s: a grid of %lld bytes is not supported", who, (long long)total);
+    hipLaunchKernelGGL(eval_grid_attrs_kernel<T>, dim3(eval_grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, images, order, boxes, preds, bar_rows, palette, grid,
+                       N, H, W, n_attr, cols, total);
+    return fd_check_launch(who);
 }
 
 extern "C" int fd_eval_grid_attrs_u8(const uint8_t* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
                                      const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream) {
-    FD_REQUIRE(images && order && boxes && preds && bar_rows && palette && grid, "fd_eval_grid_attrs_u8: null pointer");
-    FD_REQUIRE(N >= 1 && N <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "fd_eval_grid_attrs_u8: N = %d, H = %d, W = %d, supported 1..4096 each", N, H, W);
-    FD_REQUIRE(n_attr >= 1 && n_attr <= FD_EVAL_MAX_ATTR, "fd_eval_grid_attrs_u8: n_attr = %d, supported 1..%d", n_attr, FD_EVAL_MAX_ATTR);
-    FD_REQUIRE(rows >= 1 && cols >= 1 && (int64_t)rows * cols >= N && (int64_t)rows * cols < (int64_t)N + cols,
-               "fd_eval_grid_attrs_u8: a %d x %d grid does not hold %d tiles with a partly filled last row at most", rows, cols, N);
-    FD_REQUIRE(((uintptr_t)grid & 3) == 0, "fd_eval_grid_attrs_u8: the grid buffer must be 4-byte aligned");
-    const int64_t total = (int64_t)rows * (H + 2 * EG_FRAME) * cols * (W + EG_STRIP * n_attr + 2 * EG_FRAME) * 3;
-    FD_REQUIRE(total < ((int64_t)1 << 40), "fd_eval_grid_attrs_u8: a grid of %lld bytes is not supported", (long long)total);
-    const int64_t nquad = (total + 3) / 4;
-    const int64_t blocks = (nquad + 255) / 256;
-    hipLaunchKernelGGL(eval_grid_attrs_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, images, order, boxes, preds, bar_rows,
-                       palette, grid, N, H, W, n_attr, cols, total);
-    return fd_check_launch("fd_eval_grid_attrs_u8");
+    return eval_grid_attrs_launch("fd_eval_grid_attrs_u8", images, order, boxes, preds, bar_rows, palette, grid, N, H, W, n_attr, rows, cols, stream);
+}
+
+extern "C" int fd_eval_grid_attrs(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
+                                  const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream) {
+    return eval_grid_attrs_launch("fd_eval_grid_attrs", (const f16*)images, order, boxes, preds, bar_rows, palette, grid, N, H, W, n_attr, rows, cols, stream);
 }

@@ -32,7 +32,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .evaluation import BOX_WIDTH, FRAME, PALETTE_GENDER, PALETTE_RACE, STRIP, _json_safe, gap_metrics
+from .evaluation import PALETTE_GENDER, PALETTE_RACE, _json_safe, gap_metrics, grid_attrs_shape, paint_attrs_tiles  # noqa: F401
 
 PALETTE_AGE = [(255, 255, 255), (255, 140, 0), (0, 100, 0)]          # white / darkorange / darkgreen (:219-224), index = pred + 1
 PALETTES = [PALETTE_GENDER, PALETTE_RACE, PALETTE_AGE]
@@ -67,12 +67,6 @@ def parse_args(input_args=None):
 
 
 # ------------------------------------------------------------------------------------------ host statements
-def grid_attrs_shape(N, H, W, n_attr):
-    rows = int(math.sqrt(N))
-    cols = math.ceil(N / rows)
-    return rows, cols, (rows * (H + 2 * FRAME), cols * (W + STRIP * n_attr + 2 * FRAME), 3)
-
-
 def grid_attrs_order(preds, probs):
     """Tile order of ``plot_in_grid_gender_race`` (:73-108; preds / probs [2, N]: gender, race) and ``plot_in_grid_gender_race_age`` (:176-187;
     [3, N]: gender, race, age): gender 1 then 0, within it race 0..3 (within that age 0, 1), each group from the most to the least confident by the
@@ -111,41 +105,11 @@ def grid_attrs_bar_rows(probs):
 def grid_attrs_host(images, order, boxes, preds, bar_rows, palettes):
     """The numpy statement of ``fd_eval_grid_attrs_u8``: images [N,H,W,3] uint8, order [N] tile -> image, boxes [N,4] (x0,y0,x1,y1, both ends
     drawn), preds / bar_rows [n_attr,N] (pred -1 = no face, bar_rows -1 = no bar), palettes [n_attr][(r,g,b)] indexed by pred + 1 -> uint8 grid.
-    Per tile, in the reference's drawing order: pixels ``trunc((((u/255)*2-1)*0.5+0.5)*255)`` in fp32; a 4-pixel BLACK outline of the box (PIL's rule,
-    ``evaluation.grid_host``), clipped to the image; then from the innermost (last) attribute outwards a 50-pixel strip of the class colour on the
-    left and its white bar over columns 0..50 of the image as expanded so far (one column of what lies to the right included) and rows
-    0..bar_rows; a 10-pixel black frame.  Tiles past N are white."""
+    Pixels ``trunc((((u/255)*2-1)*0.5+0.5)*255)`` in fp32; outline, strips, bars, frame and the tiles past N by ``evaluation.paint_attrs_tiles``,
+    which the training-side statement ``evaluation.grid_attrs_img_host`` shares."""
     images = np.asarray(images)
-    N, H, W, _ = images.shape
-    preds, bar_rows = np.asarray(preds), np.asarray(bar_rows)
-    n_attr = preds.shape[0]
-    rows, cols, shape = grid_attrs_shape(N, H, W, n_attr)
     x = torch.from_numpy(images).float() / 255 * 2 - 1
-    pix = (x * 0.5 + 0.5).mul(255).to(torch.uint8).numpy()
-    th, tw = H + 2 * FRAME, W + STRIP * n_attr + 2 * FRAME
-    grid = np.full(shape, 255, dtype=np.uint8)
-    yy, xx = np.mgrid[0:H, 0:W]
-    for t in range(N):
-        i = int(order[t])
-        im = pix[i].copy()
-        x0, y0, x1, y1 = (int(v) for v in boxes[i])
-        hor = (((yy >= y0) & (yy < y0 + BOX_WIDTH)) | ((yy <= y1) & (yy > y1 - BOX_WIDTH))) & (xx >= x0) & (xx <= x1)
-        ya, yb = y0 + BOX_WIDTH, y1 - BOX_WIDTH + 1
-        lo, hi = (ya, yb - 1) if ya <= yb else (yb + 1, ya)
-        ver = (((xx >= x0) & (xx < x0 + BOX_WIDTH)) | ((xx <= x1) & (xx > x1 - BOX_WIDTH))) & (yy >= lo) & (yy <= hi)
-        im[hor | ver] = 0
-        for s in range(n_attr - 1, -1, -1):
-            wide = np.empty((H, im.shape[1] + STRIP, 3), dtype=np.uint8)
-            wide[:, :STRIP] = np.asarray(palettes[s][int(preds[s, i]) + 1], dtype=np.uint8)
-            wide[:, STRIP:] = im
-            if bar_rows[s, i] >= 0:
-                wide[:min(int(bar_rows[s, i]), H - 1) + 1, :STRIP + 1] = 255
-            im = wide
-        tile = np.zeros((th, tw, 3), dtype=np.uint8)
-        tile[FRAME:FRAME + H, FRAME:FRAME + im.shape[1]] = im
-        r, c = divmod(t, cols)
-        grid[r * th:(r + 1) * th, c * tw:(c + 1) * tw] = tile
-    return grid
+    return paint_attrs_tiles((x * 0.5 + 0.5).mul(255).to(torch.uint8).numpy(), order, boxes, preds, bar_rows, palettes)
 
 
 # ------------------------------------------------------------------------------------------ device side

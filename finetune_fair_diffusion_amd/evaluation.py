@@ -6,7 +6,8 @@ the classifier's probability table stays on the device, where ONE launch (``ops.
 counts and, with ``--validation grids``, one launch (``ops.eval_grid``) paints the whole annotated grid of ``plot_in_grid`` (:151-217) as
 uint8 -- the host reads back 32 integers and the finished grid instead of N x 3 x 512 x 512 images and probability tables.
 ``gap_metrics`` turns the counts into the reference's floats with the reference's fp32 operations; ``tally_host`` / ``grid_host`` are the
-plain host statements both kernels are tested against.
+plain host statements both kernels are tested against.  ``--validation grids_attrs`` and the training monitor (step.py) paint exp-3/4/5 with one
+strip per attribute instead (``device_grid_attrs``: one launch of ``ops.eval_grid_attrs_img``; host statement ``grid_attrs_img_host``).
 
 The EMA pass rewrites the 16-bit LoRA operand copies from ``bank.ema`` (``refresh_lora(ema=True)``) and back from ``bank.flat`` afterwards:
 no fp32 parameter, EMA or optimiser buffer is copied or written.
@@ -171,6 +172,92 @@ def grid_host(images, order, boxes, preds, maxprob, palette):
     return grid
 
 
+# ------------------------------------------------------------------------------------------ grids with one strip per attribute
+def grid_attrs_shape(N, H, W, n_attr):
+    rows = int(math.sqrt(N))
+    cols = math.ceil(N / rows)
+    return rows, cols, (rows * (H + 2 * FRAME), cols * (W + STRIP * n_attr + 2 * FRAME), 3)
+
+
+def paint_attrs_tiles(pix, order, boxes, preds, bar_rows, palettes):
+    """The tile rule shared by ``evaluate_images.grid_attrs_host`` and ``grid_attrs_img_host``: pix [N,H,W,3] uint8, the image pixels as they are
+    painted.  Per tile, in the reference's drawing order: a 4-pixel BLACK outline of the box (PIL's rule, ``grid_host``), clipped to the image; then
+    from the innermost (last) attribute outwards a 50-pixel strip of the class colour on the left and its white bar over columns 0..50 of the image
+    as expanded so far (one column of what lies to the right included) and rows 0..bar_rows; a 10-pixel black frame.  Tiles past N are white."""
+    N, H, W, _ = pix.shape
+    preds, bar_rows = np.asarray(preds), np.asarray(bar_rows)
+    n_attr = preds.shape[0]
+    rows, cols, shape = grid_attrs_shape(N, H, W, n_attr)
+    th, tw = H + 2 * FRAME, W + STRIP * n_attr + 2 * FRAME
+    grid = np.full(shape, 255, dtype=np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for t in range(N):
+        i = int(order[t])
+        im = pix[i].copy()
+        x0, y0, x1, y1 = (int(v) for v in boxes[i])
+        hor = (((yy >= y0) & (yy < y0 + BOX_WIDTH)) | ((yy <= y1) & (yy > y1 - BOX_WIDTH))) & (xx >= x0) & (xx <= x1)
+        ya, yb = y0 + BOX_WIDTH, y1 - BOX_WIDTH + 1
+        lo, hi = (ya, yb - 1) if ya <= yb else (yb + 1, ya)
+        ver = (((xx >= x0) & (xx < x0 + BOX_WIDTH)) | ((xx <= x1) & (xx > x1 - BOX_WIDTH))) & (yy >= lo) & (yy <= hi)
+        im[hor | ver] = 0
+        for s in range(n_attr - 1, -1, -1):
+            wide = np.empty((H, im.shape[1] + STRIP, 3), dtype=np.uint8)
+            wide[:, :STRIP] = np.asarray(palettes[s][int(preds[s, i]) + 1], dtype=np.uint8)
+            wide[:, STRIP:] = im
+            if bar_rows[s, i] >= 0:
+                wide[:min(int(bar_rows[s, i]), H - 1) + 1, :STRIP + 1] = 255
+            im = wide
+        tile = np.zeros((th, tw, 3), dtype=np.uint8)
+        tile[FRAME:FRAME + H, FRAME:FRAME + im.shape[1]] = im
+        r, c = divmod(t, cols)
+        grid[r * th:(r + 1) * th, c * tw:(c + 1) * tw] = tile
+    return grid
+
+
+def grid_attrs_img_host(images, order, boxes, preds, bar_rows, palettes):
+    """The numpy statement of ``fd_eval_grid_attrs``: images [N,3,H,W] in [-1,1] (any float dtype), order [N] tile -> image, boxes [N,4]
+    (x0,y0,x1,y1, both ends drawn), preds / bar_rows [n_attr,N] (pred -1 = no face, bar_rows -1 = no bar), palettes [n_attr][(r,g,b)] indexed by
+    pred + 1 -> uint8 grid.  Pixels by ``grid_host``'s rule, ``(x*0.5+0.5)*255`` truncated; tiles by ``paint_attrs_tiles``."""
+    x = torch.as_tensor(images).float() * 0.5 + 0.5
+    pix = x.mul(255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().cpu().numpy()
+    return paint_attrs_tiles(pix, order, boxes, preds, bar_rows, palettes)
+
+
+def grid_inputs_attrs(pd, attrs):
+    """(preds int32 [n,N], probs fp32 [n,N], bar_rows int32 [n,N], order int32 [N]) of the n = 2 or 3 attributes ``attrs`` = [(first column, k)] of
+    the table, on the table's device.  Per attribute by the rules of ``grid_inputs``: -1 where any entry is -1, the FIRST maximum wins, the
+    confidence is the row's maximum.  Bars by ``evaluate_images.grid_attrs_bar_rows`` (the age bar tests the race probability), the tile order by the
+    rule of ``evaluate_images.grid_attrs_order`` with stable sorts (``device_order``)."""
+    from .evaluate_images import device_order, grid_attrs_bar_rows
+    assert len(attrs) in (2, 3), attrs
+    preds, probs = [], []
+    for c0, k in attrs:
+        p = pd[:, c0:c0 + k]
+        valid = (p != -1).all(dim=-1)
+        mx = p.max(dim=-1).values
+        cols = torch.arange(k, device=pd.device).expand_as(p)
+        arg = torch.where(p == mx[:, None], cols, torch.full_like(cols, k)).min(dim=-1).values
+        preds.append(torch.where(valid, arg, torch.full_like(arg, -1)))
+        probs.append(mx.float())
+    preds, probs = torch.stack(preds), torch.stack(probs).contiguous()
+    return preds.to(torch.int32).contiguous(), probs, grid_attrs_bar_rows(probs), device_order(preds, probs)
+
+
+def device_grid_attrs(tr, images, boxes, pd):
+    """The annotated grid with one strip per attribute (uint8 on the device), one launch of ``ops.eval_grid_attrs_img``: exp-3/5 gender and race
+    (``plot_in_grid_gender_race``), exp-4 gender, race and age (``plot_in_grid_gender_race_age``).  The one-attribute experiments have their own
+    reference function, which draws the box in the class colour: they get ``device_grid`` (exp-1/2 gender colours, exp-6 race colours)."""
+    if len(tr.attrs) == 1:
+        return device_grid(tr, images, boxes, pd)
+    from . import ops
+    from .evaluate_images import PALETTES
+    n = len(tr.attrs)
+    preds, _, bar_rows, order = grid_inputs_attrs(pd, table_attrs(tr.attrs))
+    P = max(len(p) for p in PALETTES[:n])
+    pal = torch.tensor([p + [(255, 255, 255)] * (P - len(p)) for p in PALETTES[:n]], dtype=torch.uint8, device=images.device)
+    return ops.eval_grid_attrs_img(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, bar_rows, pal)
+
+
 # ------------------------------------------------------------------------------------------ the two functions of the reference's loop
 def draw_val_noise(n_prompts, n_images, lat):
     """``noises_val`` (:1660-1663): drawn on the global CPU generator, so a run with validation consumes it exactly where the reference does."""
@@ -264,7 +351,9 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
     vectors; the LoRA operands are switched by ``evaluation_step``.  ``prompts_tokens``: [(prompt, token tuple)]; ``noises`` [P, n, 4, h, w] on the
     host.  Returns [{metric: value}] per prompt (every rank tallies the same gathered table; only rank 0 prints and writes).  In the JSON line a
     NaN (no valid row) is written as null.  With ``mode="grids"`` rank 0 also writes
-    ``eval_{name}_{step}_{prompt}_{ori|generated}.jpg``; with ``"metrics"`` the frozen pass, which only feeds its grid, is not generated."""
+    ``eval_{name}_{step}_{prompt}_{ori|generated}.jpg`` showing the first attribute; with ``"grids_attrs"`` the grids of exp-3/4/5 carry one strip
+    per attribute (``device_grid_attrs``; the other experiments' files are the same in both modes); with ``"metrics"`` the frozen pass, which only
+    feeds its grid, is not generated."""
     from . import ops
     tr = trainer
     logs = []
@@ -277,7 +366,9 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
             toks_gen = prefix_tokens_for(tr, toks)
             toks_ori = (toks[0], toks[1], toks[2], torch.ones_like(toks[3]))
             pv = tr.prefix.vectors(ema=(which == "EMA"))
-        passes = ([("ori", te_o, unet_o, toks_ori, None)] if mode == "grids" else []) + [("generated", tr.te, tr.unet, toks_gen, pv)]
+        grids = mode in ("grids", "grids_attrs")
+        painter = device_grid_attrs if mode == "grids_attrs" else device_grid
+        passes = ([("ori", te_o, unet_o, toks_ori, None)] if grids else []) + [("generated", tr.te, tr.unet, toks_gen, pv)]
         for tag, te, unet, tk, prefix in passes:
             images = _generate(tr, te, unet, tk, nd, prefix=prefix)
             h = tr.classify_begin(images)
@@ -286,12 +377,12 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
                 counts = ops.eval_tally(pd, table_attrs(tr.attrs)).cpu()          # the evaluation's read-back: 32 integers
                 tr.last_eval_counts.append(counts)
                 logs.append(gap_metrics(tr.experiment, counts))
-            if mode == "grids":
+            if grids:
                 images_all, boxes_all = _gather_dev(tr, images), _gather_dev(tr, h["boxes"].to(tr.device, torch.int32))
                 if tr.rank == 0:
                     from PIL import Image
                     os.makedirs(imgs_dir, exist_ok=True)
-                    grid = device_grid(tr, images_all, boxes_all, pd).cpu().numpy()
+                    grid = painter(tr, images_all, boxes_all, pd).cpu().numpy()
                     Image.fromarray(grid).save(os.path.join(imgs_dir, f"eval_{name}_{step}_{prompt}_{tag}.jpg"), quality=25)
     if tr.rank == 0 and log is not None:
         keys = list(logs[0].keys()) if logs else []

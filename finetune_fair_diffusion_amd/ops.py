@@ -858,6 +858,28 @@ def eval_grid_attrs(images, order, boxes, preds, bar_rows, palette, rows=None, c
     return out
 
 
+def eval_grid_attrs_img(images, order, boxes, preds, bar_rows, palette, rows=None, cols=None, out=None):
+    """``eval_grid_attrs`` for the images a training step holds (``fd_eval_grid_attrs``): images [N,3,H,W] working dtype in [-1,1], painted as
+    ``(x*0.5+0.5)*255`` truncated; every other argument and the result as ``eval_grid_attrs``."""
+    N, C, H, W = images.shape
+    n_attr = preds.shape[0]
+    assert C == 3 and images.is_contiguous(), (images.shape, images.stride())
+    rows = int(math.sqrt(N)) if rows is None else rows
+    cols = math.ceil(N / rows) if cols is None else cols
+    pal = torch.full((max(n_attr, 1), 6, 3), 255, dtype=torch.uint8, device=images.device)
+    assert palette.dtype == torch.uint8 and palette.dim() == 3 and palette.shape[0] == n_attr and palette.shape[2] == 3, (palette.dtype, palette.shape)
+    pal[:, :palette.shape[1]] = palette
+    for t, shp in ((order, (N,)), (boxes, (N, 4)), (preds, (n_attr, N)), (bar_rows, (n_attr, N))):
+        assert t.dtype == torch.int32 and tuple(t.shape) == shp and t.is_contiguous(), (t.dtype, t.shape, shp)
+    shape = (rows * (H + 20), cols * (W + 50 * n_attr + 20), 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=images.device)
+    # the entry point cannot see the size of the buffer it fills
+    assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape, (out.dtype, out.shape, shape)
+    _call("fd_eval_grid_attrs", _p(_chk(images)), _p(order), _p(boxes), _p(preds), _p(bar_rows), _p(pal), _p(out), N, H, W, n_attr, rows, cols, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- text-encoder attention
 def small_attn_fwd(q, k, v, key_valid, B, H, T, d, scale, causal=True, save_p=False):
     o = torch.empty_like(q)

@@ -270,6 +270,11 @@ class FairnessTrainer:
         self.ot_on_device = os.environ.get("FD_OT_HOST") is None
         self._ot_stream = torch.cuda.Stream(device=self.device)
         self._tgt = None
+        # training monitor (--train_monitor; train.py sets both): "off" / "metrics" / "plots", and whether THIS step is one the reference plots
+        # (``step % train_plot_every_n_iter == 0``).  ``last_monitor``: what the last step's monitor produced (``_monitor_side``); None when off.
+        self.monitor = "off"
+        self.monitor_plot = False
+        self.last_monitor = self._mon = None
         if self.enumerated_targets:      # the table of the usual global face count (every image has a face); other counts are built on the worker
             composition_table(world_size * getattr(args, "train_images_per_prompt_GPU", 0))
 
@@ -682,6 +687,38 @@ class FairnessTrainer:
         pre["k"] = pre["S"]
         torch.cuda.current_stream().wait_stream(side)
 
+    # ------------------------------------------------------------------ training monitor (--train_monitor; the reference's per-batch logs and plots)
+    def _to_pinned(self, t):
+        """Device tensor -> fresh pinned host tensor, copied asynchronously on the current stream (read once ``_mon["event"]`` has passed)."""
+        host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        host.copy_(t, non_blocking=True)
+        return host
+
+    def _monitor_side(self, tag, images, h, tally):
+        """One side of the monitor -- "generated" (R1, exp-3 :1978-2011) or "ori" (R2, :2052-2075) -- enqueued on the step's stream behind the
+        producers of ``images`` and of ``classify_begin``'s handle ``h``; nothing is read back here and no random number is drawn.  The [B, sum k]
+        probability table is gathered in rank order; with ``tally`` one ``ops.eval_tally`` launch reduces it to the 32 counts of
+        ``evaluation.gap_metrics`` and they start their way to pinned memory.  On a plot step images and boxes are gathered too (every rank takes
+        part, as in the reference) and rank 0 paints the grid in one launch (``evaluation.device_grid_attrs``), which follows the counts."""
+        from . import evaluation as EV
+        mon = self._mon
+        plot = self.monitor == "plots" and self.monitor_plot
+        if not (tally or plot):
+            return
+        pd = EV._gather_dev(self, EV.probability_table(self, h))
+        mon["tables"][tag] = pd
+        if tally:
+            mon["counts"] = self._to_pinned(ops.eval_tally(pd, EV.table_attrs(self.attrs)))
+        if plot:
+            images_all = EV._gather_dev(self, images)
+            bx = h["boxes"].to(torch.int32)
+            boxes_all = EV._gather_dev(self, bx.to(self.device) if bx.is_cuda else _h2d(bx, self.device))
+            mon["images"][tag], mon["boxes"][tag] = images_all, boxes_all
+            if self.rank == 0:
+                mon["grids"][tag] = self._to_pinned(EV.device_grid_attrs(self, images_all, boxes_all, pd))
+        mon["event"] = torch.cuda.Event()
+        mon["event"].record()
+
     def allreduce_grads(self):
         """(2) ONE all-reduce(SUM) per flat fp32 LoRA-gradient buffer (RCCL over xGMI on the GPU box)."""
         if getattr(self, "collectives", self.world > 1):
@@ -725,6 +762,8 @@ class FairnessTrainer:
         else:
             noises = noises.to(dev, F32)
         out = {}
+        self.last_monitor = None
+        mon = self._mon = dict(tables={}, images={}, boxes={}, grids={}) if self.monitor != "off" else None
         for bank in self.banks:
             bank.grad.zero_()
         vb = args.val_GPU_batch_size
@@ -822,6 +861,8 @@ class FairnessTrainer:
         # ---- dynamic targets from the global batch (:1805-1837): gathered now, solved underneath R2, consumed by R3's loss
         self.start_dynamic_targets(per, B)
         out.update(images=images)
+        if mon is not None:
+            self._monitor_side("generated", images, h_g, tally=True)
         (rb if dv else out).update(probs=per[0]["probs"], preds=per[0]["preds"])
         # ---- R2: images from the frozen original models (:1844-1858)
         if conc:
@@ -855,6 +896,8 @@ class FairnessTrainer:
             if not _NO_TAIL_REORDER:                 # the read-back of R2's logits comes after its feature encoders have been enqueued
                 ind_o, boxes_o, per_o = self.classify_dev(h_o) if dv else self.classify_end(h_o)
         out.update(images_ori=images_ori)
+        if mon is not None:
+            self._monitor_side("ori", images_ori, h_o, tally=False)
         (rb if dv else out).update(preds_ori=per_o[0]["preds"], probs_ori=per_o[0]["probs"])
         tgt = self.finish_dynamic_targets()
         targets = tgt[0][0]
@@ -1127,6 +1170,10 @@ class FairnessTrainer:
                 out["loss"] = out["loss"] + args.weight_loss_img * out["dynamic_weights"] * (out["loss_CLIP"] + out["loss_DINO"])
             if "loss_face" in out:
                 out["loss"] = out["loss"] + args.weight_loss_face * out["loss_face"]
+        if mon is not None:
+            # behind the step's own read-back (``sync_and_update``), which has drained the stream the copies were queued on: no further wait
+            mon.pop("event").synchronize()
+            self.last_monitor, self._mon = mon, None
         self._mark("end")
         return out
 

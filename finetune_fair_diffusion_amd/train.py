@@ -5,14 +5,19 @@
 
 Same flags, YAML overlay, seeding (``set_seed(seed, device_specific=True)`` :693, prompt order from
 ``random.seed(seed+1)`` :914-921, S drawn on rank 0 from range(19,24) and broadcast :1779-1781, per-rank CPU noise
-:1746-1749), checkpoint cadence (:2050-2068) and resume (:1697-1725) as the reference; wandb and the training plots are
-replaced by one JSON line per step on rank 0.  One process per GPU; RCCL through torch.distributed ("nccl").
+:1746-1749), checkpoint cadence (:2050-2068) and resume (:1697-1725) as the reference; wandb is
+replaced by one JSON line per step on rank 0 (the training plots: ``--train_monitor`` below).  One process per GPU; RCCL through torch.distributed ("nccl").
 
 Validation (``evaluation_step`` :1659-1690) is opt-in: ``--validation metrics`` runs it at step 0 and every ``--evaluate_every_n_iter`` steps for
 the live and the EMA weights and prints one more JSON line per pass (``{"eval": "main"|"EMA", "step", "per_prompt", "mean"}`` with the
 reference's gap metrics); ``--validation grids`` also writes the annotated image grids to ``<output_dir>/imgs``.  Its noise is drawn from the
 global CPU generator at the reference's points, so the training noise of such a run is the reference's with evaluation enabled.  With
 ``--validation off`` (default) nothing changes.
+
+The training monitor is opt-in as well: ``--train_monitor metrics`` adds the reference's per-batch gap metrics to every step's JSON line
+(``train_gender_gap``, ``train_race_gap``, ... of the gathered probability table the finetuned model's images were classified into, tallied on the
+device; ``num_faces`` / ``num_faces_total``), ``--train_monitor plots`` also writes the reference's train plots
+``<output_dir>/imgs/train-{global_step}_generated.jpg`` / ``_ori.jpg`` on the steps the reference writes them (``train_plot_number``).
 """
 import json
 import math
@@ -97,6 +102,14 @@ def peek_draw(draw, before=None):
 def evaluation_due(validation, global_step, every):
     """The reference's two points (:1739-1740, :2047-2048): before the first step of a fresh run, and after a step whose number divides."""
     return validation != "off" and every > 0 and global_step % every == 0
+
+
+def train_plot_number(step_in_epoch, global_step, every):
+    """The number in ``train-{n}_generated.jpg`` / ``train-{n}_ori.jpg`` when the reference plots this step, else None (exp-3 :1989-1990,
+    :2063-2064; exp-1 :1814, :1873): it tests ``step % train_plot_every_n_iter == 0`` on the step's index INSIDE its epoch and names the files by
+    ``global_step`` as it stands there -- the number of steps completed BEFORE this one (the increment comes after the update, :2250), so the first
+    step of a run writes ``train-0_*``.  A resumed run keeps the epoch's own indices (the skipped steps are counted, :1905-1907)."""
+    return global_step if every > 0 and step_in_epoch % every == 0 else None
 
 
 def load_prompts(args):
@@ -207,10 +220,11 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
     B = args.train_images_per_prompt_GPU
     validation = getattr(args, "validation", "off")
     prompts_val = []
+    imgs_dir = os.path.join(args.output_dir, "imgs")
     if validation != "off":
         from . import evaluation
         prompts_val = evaluation.validation_prompts(_occupation_data(args))
-        imgs_dir = os.path.join(args.output_dir, "imgs")
+    monitor = trainer.monitor = getattr(args, "train_monitor", "off")
 
     def draw_val():
         return evaluation.draw_val_noise(len(prompts_val), args.val_images_per_prompt_GPU, lat)
@@ -252,6 +266,8 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
         if i + 1 < len(plan) and global_step + 1 < args.max_train_steps and os.environ.get("FD_NO_R2_PREFETCH") is None:
             p_n, noises_n, S_n = peek(plan[i + 1][2], evaluation_due(validation, global_step + 1, args.evaluate_every_n_iter))
             nxt = dict(tokens_ori=r2_tokens(tokenizer(p_n)), noises=noises_n, S=S_n)
+        plot_no = train_plot_number(step, global_step, args.train_plot_every_n_iter) if monitor == "plots" else None
+        trainer.monitor_plot = plot_no is not None
         if trainer.prefix is not None:
             # exp-2 (:1846, :1895, :1954, :2001): the finetuned side sees "".join(prefix_tokens) + prompt with the pipeline's negative
             # prompt (no padding mask); the original side sees the plain prompt, its empty prompt encoded without a mask as well
@@ -270,6 +286,16 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
                        loss_face=(float(out["loss_face"][out["loss_face"] != -1].mean()) if (out["loss_face"] != -1).any() else None) if "loss_face" in out else None,
                        p_class1_mean=float(out["probs"][:, 1][out["probs"][:, 1] != -1].mean()) if bool((out["probs"] != -1).any()) else None,
                        seconds=round(time.time() - t0, 3))
+            if monitor != "off":
+                from .evaluation import _json_safe, gap_metrics
+                mon = trainer.last_monitor
+                rec.update(_json_safe({f"train_{k}": v for k, v in gap_metrics(experiment, mon["counts"]).items()}),
+                           num_faces=int(mon["counts"][0]), num_faces_total=int(mon["tables"]["generated"].shape[0]))
+                if mon["grids"]:
+                    from PIL import Image
+                    os.makedirs(imgs_dir, exist_ok=True)
+                    for tag, grid in mon["grids"].items():          # painted on the device inside the step; encoded here, behind its read-back
+                        Image.fromarray(grid.numpy()).save(os.path.join(imgs_dir, f"train-{plot_no}_{tag}.jpg"), quality=25)
             (log or print)(json.dumps(rec))
         if evaluation_due(validation, global_step, args.evaluate_every_n_iter):      # :2047-2048
             evaluate(global_step)

@@ -378,6 +378,15 @@ int fd_crop_resize_u8_fwd(const uint8_t* img, const int32_t* boxes, float fill, 
 int fd_eval_grid_attrs_u8(const uint8_t* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
                           const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream);
 
+/* ---- training monitor (step.py, evaluation.device_grid_attrs; the train plots of exp-3/5 1-main-debias.py :1989-2002, :2063-2075 with
+ * plot_in_grid_gender_race :152-255, exp-4 :2088, :2176 with plot_in_grid_gender_race_age :152-244).  Additive: FD_ABI_VERSION is unchanged.
+ * fd_eval_grid_attrs_u8 for the images a training step holds: images [N,3,H,W] working dtype in [-1,1] -> grid [rows*(H+20), cols*(W+50*n_attr+20), 3]
+ * uint8 (4-byte aligned) in one launch.  Pixels (x*0.5+0.5)*255 truncated (two fp32 roundings, as fd_eval_grid_u8); everything else -- black outline,
+ * strips from the outside in, inclusive white bars with outer strips winning, black frame, white tiles past N, no index text -- and every argument
+ * and refusal as fd_eval_grid_attrs_u8. */
+int fd_eval_grid_attrs(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
+                       const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
