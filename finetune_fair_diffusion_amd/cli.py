@@ -16,6 +16,10 @@ cannot be set from YAML and booleans follow Python's ``bool(value)`` -- plus the
                          gains ``train_<gap metric>`` of the gathered batch, ``num_faces`` and ``num_faces_total``; plots: also, every
                          ``--train_plot_every_n_iter`` steps of an epoch, ``<output_dir>/imgs/train-{global_step}_{generated|ori}.jpg``.  "off"
                          leaves the run exactly as without the flag; no mode draws a random number or changes a result of the step
+  --index_font           PATH of a TrueType font file, or "default" for Pillow's embedded scalable font: the validation grids and the train plots
+                         print each image's index (in the gathered batch) on its tile, as the reference does with Arial Bold (``plot_in_grid``
+                         :199-200) -- the number pairs a tile of the ``_ori`` grid with its tile of the ``_generated`` grid.  Not given (default):
+                         no index text, the grids as before.  ``--index_font_size`` (default 100, the reference's) is the point size
 
 The multi-attribute experiments change a few flags and defaults (exp-3-debias-gender-race/1-main-debias.py:343-660,
 exp-4-debias-gender-race-age/...:343-672, exp-5-...:343-690; exp-2-debias-gender-token/...:453-780 drops the two LoRA switches and adds
@@ -135,7 +139,7 @@ def build_parser(experiment="exp-1"):
 
 
 EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="synthetic", num_classifier_logits=80, lora_up_std=0.0, validation="off",
-                      train_monitor="off")
+                      train_monitor="off", index_font=None, index_font_size=100)
 
 
 def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
@@ -148,6 +152,8 @@ def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
         p.add_argument("--lora_up_std", type=float, default=0.0)
         p.add_argument("--validation", type=str, default="off", choices=["off", "metrics", "grids", "grids_attrs"])
         p.add_argument("--train_monitor", type=str, default="off", choices=["off", "metrics", "plots"])
+        p.add_argument("--index_font", type=str, default=None, help="font file, or 'default': print the image index on every grid tile; not given: no text")
+        p.add_argument("--index_font_size", type=int, default=100)
     args = p.parse_args(input_args) if input_args is not None else p.parse_args()
     if args.config:
         with open(args.config, "r") as f:

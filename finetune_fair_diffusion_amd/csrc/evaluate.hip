@@ -331,3 +331,64 @@ extern "C" int fd_eval_grid_attrs(const void* images, const int32_t* order, cons
                                   const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream) {
     return eval_grid_attrs_launch("fd_eval_grid_attrs", (const f16*)images, order, boxes, preds, bar_rows, palette, grid, N, H, W, n_attr, rows, cols, stream);
 }
+
+// ---------------------------------------------------------------- fd_eval_grid_labels_u8
+// The reference's index text (``img_pil_draw.text((400, 400), f"{idx.item()}", font=fnt)``, plot_in_grid :199-200 and its two- / three-strip
+// siblings) as an in-place pass over a grid one of the three painters has written: tile t gets the 8-bit coverage mask of the string str(order[t]),
+// rasterised on the host (evaluation.IndexLabels), blended as white ink by PIL's rule and clipped to the tile's inner area.  The descriptor table is
+// device memory nobody has validated: every entry is checked against ``n_labels`` / ``mask_bytes`` before a mask byte is read, and a tile whose entry
+// fails gets nothing.  blockIdx.y = tile, blockIdx.x strides over the visible mask rows, threads run along a mask row: mask reads are contiguous and
+// the grid accesses are contiguous 3-byte pixels; each thread reads and writes only its own pixel.
+#define EG_LABEL_ROW_BLOCKS 128
+
+// PIL's ``MULDIV255``-style blend of ink 255 under coverage m (ImagingDraw's ``BLEND`` for 8-bit channels)
+__device__ __forceinline__ uint32_t eval_label_blend(uint32_t a, uint32_t m) {
+    const uint32_t t = a * (255u - m) + 255u * m + 128u;
+    return ((t >> 8) + t) >> 8;
+}
+
+__global__ __launch_bounds__(256) void eval_grid_labels_kernel(uint8_t* __restrict__ grid, const int32_t* __restrict__ order, const uint8_t* __restrict__ masks,
+                                                               int64_t mask_bytes, const int32_t* __restrict__ desc, int n_labels, int N, int H, int W, int n_strip,
+                                                               int cols, int x, int y) {
+    const int t = blockIdx.y;
+    if (t >= N) return;
+    const int i = order[t];
+    if (i < 0 || i >= N || i >= n_labels) return;      // a malformed order entry is a white tile (eval_tile_locate); no mask for this index
+    const int32_t* d = desc + (int64_t)i * 5;
+    const int64_t w = d[0], h = d[1], boff = d[4];
+    if (w <= 0 || h <= 0 || boff < 0 || w * h > mask_bytes || boff > mask_bytes - w * h) return;
+    const int64_t IW = W + EG_STRIP * n_strip;
+    const int64_t X0 = (int64_t)x + d[2], Y0 = (int64_t)y + d[3];      // the mask's top-left inside the strip-expanded image
+    const int64_t c_lo = X0 < 0 ? -X0 : 0, c_hi = IW - X0 < w ? IW - X0 : w;
+    const int64_t r_lo = Y0 < 0 ? -Y0 : 0, r_hi = H - Y0 < h ? H - Y0 : h;
+    if (c_lo >= c_hi || r_lo >= r_hi) return;
+    const int tw = W + EG_STRIP * n_strip + 2 * EG_FRAME, th = H + 2 * EG_FRAME;
+    const int64_t GW = (int64_t)cols * tw;
+    const int tr = t / cols, tc = t - tr * cols;
+    for (int64_t r = r_lo + blockIdx.x; r < r_hi; r += gridDim.x) {
+        const uint8_t* mrow = masks + boff + r * w;
+        uint8_t* grow = grid + (((int64_t)tr * th + EG_FRAME + Y0 + r) * GW + (int64_t)tc * tw + EG_FRAME + X0) * 3;
+        for (int64_t c = c_lo + threadIdx.x; c < c_hi; c += blockDim.x) {
+            const uint32_t m = mrow[c];
+            if (m == 0) continue;      // the blend is the identity there
+            uint8_t* px = grow + c * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) px[k] = (uint8_t)eval_label_blend(px[k], m);
+        }
+    }
+}
+
+extern "C" int fd_eval_grid_labels_u8(uint8_t* grid, const int32_t* order, const uint8_t* masks, int64_t mask_bytes, const int32_t* desc, int n_labels, int N, int H,
+                                      int W, int n_strip, int rows, int cols, int x, int y, void* stream) {
+    FD_REQUIRE(grid && order && masks && desc, "fd_eval_grid_labels_u8: null pointer");
+    FD_REQUIRE(N >= 1 && N <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "fd_eval_grid_labels_u8: N = %d, H = %d, W = %d, supported 1..4096 each", N, H, W);
+    FD_REQUIRE(n_strip >= 1 && n_strip <= FD_EVAL_MAX_ATTR, "fd_eval_grid_labels_u8: n_strip = %d, supported 1..%d", n_strip, FD_EVAL_MAX_ATTR);
+    FD_REQUIRE(rows >= 1 && cols >= 1 && (int64_t)rows * cols >= N && (int64_t)rows * cols < (int64_t)N + cols,
+               "fd_eval_grid_labels_u8: a %d x %d grid does not hold %d tiles with a partly filled last row at most", rows, cols, N);
+    FD_REQUIRE(n_labels >= 1, "fd_eval_grid_labels_u8: n_labels = %d, at least 1", n_labels);
+    FD_REQUIRE(mask_bytes >= 0, "fd_eval_grid_labels_u8: mask_bytes = %lld, must not be negative", (long long)mask_bytes);
+    const unsigned bx = (unsigned)(H < EG_LABEL_ROW_BLOCKS ? H : EG_LABEL_ROW_BLOCKS);
+    hipLaunchKernelGGL(eval_grid_labels_kernel, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, grid, order, masks, mask_bytes, desc, n_labels, N, H, W,
+                       n_strip, cols, x, y);
+    return fd_check_launch("fd_eval_grid_labels_u8");
+}

@@ -9,7 +9,8 @@ reads ``generated_imgs_dir/prompt_{i}/img_{j}.jpg`` (what ``generate.py`` writes
   * ``test_results.pkl`` -- ``[face_indicators_all, face_bboxs_all, gender_logits_all, race_logits_all, age_logits_all]``, each a dict from prompt
     index to a CPU tensor (bool [N], int64 [N,4], float32 [N,k]): the reference's file (:696-709);
   * ``prompt_{i}.jpg`` -- the annotated grid of ``plot_in_grid_gender_race`` (:65-168; ``--grid gender_race_age``: ``plot_in_grid_gender_race_age``
-    :171-263, which the reference's main carries commented out), painted on the device in one launch and saved with ``quality=25``;
+    :171-263, which the reference's main carries commented out), painted on the device in one launch and saved with ``quality=25``; with
+    ``--index_font PATH|default`` each tile carries its image's index as in the reference (:150-151; one more launch, ``evaluation.IndexLabels``);
   * ``metrics.json`` (build addition) -- per prompt and as a mean, exp-4's validation numbers (``evaluation.gap_metrics("exp-4", ...)``) of the three
     test classifiers' softmax table, tallied on the device (``ops.eval_tally``): 32 integers per prompt are read back for it.
 
@@ -32,7 +33,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .evaluation import PALETTE_GENDER, PALETTE_RACE, _json_safe, gap_metrics, grid_attrs_shape, paint_attrs_tiles  # noqa: F401
+from .evaluation import (LABEL_FONT_SIZE, PALETTE_GENDER, PALETTE_RACE, IndexLabels, _json_safe, draw_labels, gap_metrics, grid_attrs_shape,  # noqa: F401
+                         paint_attrs_tiles)
 
 PALETTE_AGE = [(255, 255, 255), (255, 140, 0), (0, 100, 0)]          # white / darkorange / darkgreen (:219-224), index = pred + 1
 PALETTES = [PALETTE_GENDER, PALETTE_RACE, PALETTE_AGE]
@@ -63,6 +65,11 @@ def parse_args(input_args=None):
     a("--face_provider", type=str, default="synthetic", help="(build addition) 'synthetic' or 'detector', as in train.py")
     a("--grid", type=str, default="gender_race", choices=["gender_race", "gender_race_age", "off"],
       help="(build addition) which of the reference's two grids to paint; its main runs gender_race")
+    # the two flags below are absent from the namespace unless given (argparse.SUPPRESS): without them the arguments are the reference's plus --grid etc.
+    a("--index_font", type=str, default=argparse.SUPPRESS,
+      help="(build addition) PATH of a TrueType font file, or 'default' for Pillow's embedded one: print each image's index on its tile as the reference "
+           "does with Arial Bold; not given: no index text")
+    a("--index_font_size", type=int, default=argparse.SUPPRESS, help=f"(build addition) point size of --index_font; default {LABEL_FONT_SIZE}, the reference's")
     return p.parse_args(input_args) if input_args is not None else p.parse_args()
 
 
@@ -133,9 +140,10 @@ def device_order(preds, probs):
     return by_conf[torch.sort(group[by_conf], stable=True).indices].to(torch.int32).contiguous()
 
 
-def device_grid(images, boxes, probs_list, which):
+def device_grid(images, boxes, probs_list, which, labels=None):
     """The annotated grid (uint8 on the device) of one prompt: images [N,H,W,3] uint8, boxes [N,4] int32, probs_list = the three softmax tables
-    (gender, race, age) on the device.  Predictions, bars and the tile order are torch on the device; the painting is one launch."""
+    (gender, race, age) on the device.  Predictions, bars and the tile order are torch on the device; the painting is one launch.  ``labels``: an
+    ``evaluation.IndexLabels`` -- one more launch behind the painter draws the index text (:150-151, :245-246); None: no text."""
     from . import ops
     n_attr = 2 if which == "gender_race" else 3
     pm = [_first_argmax(p) for p in probs_list[:n_attr]]
@@ -143,7 +151,9 @@ def device_grid(images, boxes, probs_list, which):
     probs = torch.stack([m for _, m in pm]).float().contiguous()
     P = max(len(p) for p in PALETTES[:n_attr])
     pal = torch.tensor([p + [(255, 255, 255)] * (P - len(p)) for p in PALETTES[:n_attr]], dtype=torch.uint8, device=images.device)
-    return ops.eval_grid_attrs(images, device_order(preds, probs), boxes, preds, grid_attrs_bar_rows(probs), pal)
+    order = device_order(preds, probs)
+    grid = ops.eval_grid_attrs(images, order, boxes, preds, grid_attrs_bar_rows(probs), pal)
+    return draw_labels(grid, order, labels, images.shape[1], images.shape[2], n_attr)
 
 
 def synthetic_classifier_state(which):
@@ -191,6 +201,7 @@ def main(args, face_provider=None, log=print):
             sd = load_classifier(path, ATTR_K[which])
         classifiers.append(MobileNetV3Large(sd, device, ATTR_K[which]))
 
+    labels = IndexLabels(args.index_font, getattr(args, "index_font_size", LABEL_FONT_SIZE)) if getattr(args, "index_font", None) and args.grid != "off" else None
     folders = _numbered(glob.glob(os.path.join(args.generated_imgs_dir, "prompt_*")), lambda x: int(x.split("_")[-1]))
     os.makedirs(args.save_dir, exist_ok=True)
     results = [{}, {}, {}, {}, {}]          # indicators, boxes, gender / race / age logits
@@ -236,7 +247,7 @@ def main(args, face_provider=None, log=print):
             table = torch.where(ind.to(device)[:, None], table, torch.full_like(table, -1.0)).contiguous()
             metrics[prompt_idx] = gap_metrics("exp-4", ops.eval_tally(table, TABLE_ATTRS).cpu())
             if args.grid != "off":
-                grid = device_grid(imgs_d, boxes.to(device), probs, args.grid).cpu().numpy()
+                grid = device_grid(imgs_d, boxes.to(device), probs, args.grid, labels=labels).cpu().numpy()
                 Image.fromarray(grid).save(os.path.join(args.save_dir, f"prompt_{prompt_idx}.jpg"), quality=25)
             results[0][prompt_idx] = ind
             results[1][prompt_idx] = boxes.to(torch.int64)

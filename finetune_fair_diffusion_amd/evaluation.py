@@ -8,6 +8,8 @@ uint8 -- the host reads back 32 integers and the finished grid instead of N x 3 
 ``gap_metrics`` turns the counts into the reference's floats with the reference's fp32 operations; ``tally_host`` / ``grid_host`` are the
 plain host statements both kernels are tested against.  ``--validation grids_attrs`` and the training monitor (step.py) paint exp-3/4/5 with one
 strip per attribute instead (``device_grid_attrs``: one launch of ``ops.eval_grid_attrs_img``; host statement ``grid_attrs_img_host``).
+``IndexLabels`` (``--index_font``) adds the reference's index text to any of these grids: the strings are rasterised once on the host with the
+caller's font and one more launch (``ops.eval_grid_labels``; host statement ``labels_host``) blends them into the painted grid.
 
 The EMA pass rewrites the 16-bit LoRA operand copies from ``bank.ema`` (``refresh_lora(ema=True)``) and back from ``bank.flat`` afterwards:
 no fp32 parameter, EMA or optimiser buffer is copied or written.
@@ -243,19 +245,126 @@ def grid_inputs_attrs(pd, attrs):
     return preds.to(torch.int32).contiguous(), probs, grid_attrs_bar_rows(probs), device_order(preds, probs)
 
 
-def device_grid_attrs(tr, images, boxes, pd):
+def device_grid_attrs(tr, images, boxes, pd, labels=None):
     """The annotated grid with one strip per attribute (uint8 on the device), one launch of ``ops.eval_grid_attrs_img``: exp-3/5 gender and race
     (``plot_in_grid_gender_race``), exp-4 gender, race and age (``plot_in_grid_gender_race_age``).  The one-attribute experiments have their own
-    reference function, which draws the box in the class colour: they get ``device_grid`` (exp-1/2 gender colours, exp-6 race colours)."""
+    reference function, which draws the box in the class colour: they get ``device_grid`` (exp-1/2 gender colours, exp-6 race colours).
+    ``labels``: an ``IndexLabels`` -- the index text is drawn by one more launch behind the painter; None: the grid as it was without it."""
     if len(tr.attrs) == 1:
-        return device_grid(tr, images, boxes, pd)
+        return device_grid(tr, images, boxes, pd, labels=labels)
     from . import ops
     from .evaluate_images import PALETTES
     n = len(tr.attrs)
     preds, _, bar_rows, order = grid_inputs_attrs(pd, table_attrs(tr.attrs))
     P = max(len(p) for p in PALETTES[:n])
     pal = torch.tensor([p + [(255, 255, 255)] * (P - len(p)) for p in PALETTES[:n]], dtype=torch.uint8, device=images.device)
-    return ops.eval_grid_attrs_img(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, bar_rows, pal)
+    grid = ops.eval_grid_attrs_img(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, bar_rows, pal)
+    return draw_labels(grid, order, labels, images.shape[2], images.shape[3], n)
+
+
+# ------------------------------------------------------------------------------------------ the index text
+LABEL_XY = (400, 400)                # ``img_pil_draw.text((400, 400), f"{idx.item()}", align="left", font=fnt)`` (exp-1 :199-200)
+LABEL_FONT_SIZE = 100
+
+
+def label_blend(a, m):
+    """PIL's blend of white ink under coverage m into the 8-bit channel value a: ``t = a*(255-m) + 255*m + 128; ((t >> 8) + t) >> 8``."""
+    t = np.asarray(a, dtype=np.uint32) * (255 - np.asarray(m, dtype=np.uint32)) + 255 * np.asarray(m, dtype=np.uint32) + 128
+    return (((t >> 8) + t) >> 8).astype(np.uint8)
+
+
+def labels_host(grid, order, masks, desc, H, W, n_strip, cols, xy=LABEL_XY):
+    """The numpy statement of ``fd_eval_grid_labels_u8``: a copy of ``grid`` [rows*(H+20), cols*(W+50*n_strip+20), 3] uint8 (painted by ``grid_host``,
+    ``grid_attrs_img_host`` or ``evaluate_images.grid_attrs_host``) with the index text.  Tile t shows image i = order[t] and gets label i: the w x h
+    coverage mask at ``masks[byte_offset:]`` with desc[i] = (w, h, off_x, off_y, byte_offset), its top-left at (xy[0] + off_x, xy[1] + off_y) of the
+    tile's inner area (W + 50*n_strip by H, inside the frame).  What falls inside that area is blended as white ink (``label_blend``) over whatever the
+    painter left there; the rest is clipped.  A tile whose order entry is outside [0, N), whose label the table does not hold, or whose descriptor
+    does not lie inside ``masks`` gets nothing."""
+    out = np.array(grid, dtype=np.uint8, copy=True)
+    masks, desc = np.asarray(masks, dtype=np.uint8).reshape(-1), np.asarray(desc, dtype=np.int64).reshape(-1, 5)
+    N, IW = len(order), W + STRIP * n_strip
+    th, tw = H + 2 * FRAME, IW + 2 * FRAME
+    for t in range(N):
+        i = int(order[t])
+        if not (0 <= i < N and i < len(desc)):
+            continue
+        w, h, ox, oy, off = (int(v) for v in desc[i])
+        if w <= 0 or h <= 0 or off < 0 or off + w * h > masks.size:
+            continue
+        m = masks[off:off + w * h].reshape(h, w)
+        x0, y0 = int(xy[0]) + ox, int(xy[1]) + oy
+        ca, cb, ra, rb = max(0, -x0), min(w, IW - x0), max(0, -y0), min(h, H - y0)
+        if ca >= cb or ra >= rb:
+            continue
+        r, c = divmod(t, cols)
+        inner = out[r * th + FRAME:r * th + FRAME + H, c * tw + FRAME:c * tw + FRAME + IW]
+        view = inner[y0 + ra:y0 + rb, x0 + ca:x0 + cb]
+        view[...] = label_blend(view, m[ra:rb, ca:cb, None])
+    return out
+
+
+class IndexLabels:
+    """The index text of the annotated grids: the strings "0", "1", ... rasterised with the caller's font as ``ImageDraw.text`` rasterises them for
+    an RGB image with default arguments -- ``font.getmask2(s, "L", anchor="la")``, each string as a whole (advances are fractional and digits kern:
+    concatenated digit masks are not the string's mask).  ``font``: the path of a TrueType / OpenType file (the reference uses Arial Bold, which is
+    the user's to supply), or "default" for Pillow's embedded scalable font.  ``atlas(n, device)`` hands the kernel its two device buffers; ``xy`` is
+    where the grid helpers anchor the text (the reference's (400, 400) lies outside an image smaller than that: such grids show no text)."""
+
+    def __init__(self, font, size=LABEL_FONT_SIZE, xy=LABEL_XY):
+        from PIL import ImageFont, features
+        if not features.check("freetype2"):
+            raise RuntimeError("index labels need a Pillow built with FreeType (PIL.features.check('freetype2') is False): install one, or run without --index_font")
+        if int(size) < 1:
+            raise ValueError(f"index label font size {size}: at least 1")
+        if font == "default":
+            if not hasattr(ImageFont, "load_default") or "size" not in ImageFont.load_default.__code__.co_varnames:
+                raise RuntimeError("this Pillow has no scalable embedded font (ImageFont.load_default(size) needs Pillow 10.1): pass the path of a font file")
+            self.font = ImageFont.load_default(int(size))
+        else:
+            if not os.path.isfile(font):
+                raise FileNotFoundError(f"index label font {font!r} is not a file (pass the path of a .ttf / .otf file, or 'default')")
+            self.font = ImageFont.truetype(font, int(size))
+        self.name, self.size = font, int(size)
+        self.xy = (int(xy[0]), int(xy[1]))          # the text's anchor inside the strip-expanded image; the reference's is fixed at (400, 400)
+        self._masks, self._desc, self._bytes = [], [], 0          # host rasters of labels 0 .. len-1, grown on demand
+        self._atlas = {}                                          # (n, device) -> (masks, desc) on the device
+
+    def raster(self, text):
+        """(mask uint8 [h,w], (w, h, off_x, off_y)) of one string: what ``ImageDraw.text(xy, text, font=font)`` blends at xy + (off_x, off_y)."""
+        core, (ox, oy) = self.font.getmask2(text, "L", anchor="la")
+        w, h = core.size
+        return np.frombuffer(bytes(core), dtype=np.uint8, count=w * h).reshape(h, w), (w, h, int(ox), int(oy))
+
+    def host(self, n):
+        """(masks uint8 [bytes], desc int32 [n,5] = (w, h, off_x, off_y, byte_offset)) of the labels "0" .. str(n-1), packed in label order."""
+        assert n >= 1, n
+        for i in range(len(self._desc), n):
+            mask, d = self.raster(str(i))
+            self._masks.append(mask.reshape(-1))
+            self._desc.append(d + (self._bytes,))
+            self._bytes += mask.size
+        desc = np.asarray(self._desc[:n], dtype=np.int32).reshape(n, 5)
+        masks = np.concatenate(self._masks[:n]) if n else np.zeros(0, dtype=np.uint8)
+        return np.ascontiguousarray(masks), desc
+
+    def atlas(self, n, device):
+        device = torch.device(device)
+        key = (int(n), str(device))
+        if key not in self._atlas:
+            masks, desc = self.host(int(n))
+            if masks.size == 0:
+                raise RuntimeError(f"index label font {self.name!r} draws nothing for the digits")
+            self._atlas[key] = (torch.from_numpy(masks).to(device), torch.from_numpy(desc).to(device))
+        return self._atlas[key]
+
+
+def draw_labels(grid, order, labels, H, W, n_strip):
+    """The index text onto a grid the painter has just written, on the same stream directly behind it (one launch); ``labels`` None: nothing."""
+    if labels is None:
+        return grid
+    from . import ops
+    masks, desc = labels.atlas(order.shape[0], grid.device)
+    return ops.eval_grid_labels(grid, order, masks, desc, H, W, n_strip, xy=getattr(labels, "xy", LABEL_XY))
 
 
 # ------------------------------------------------------------------------------------------ the two functions of the reference's loop
@@ -329,14 +438,15 @@ def grid_inputs(pd, k0):
     return preds.contiguous(), maxprob.float().contiguous(), order.contiguous()
 
 
-def device_grid(tr, images, boxes, pd):
+def device_grid(tr, images, boxes, pd, labels=None):
     """The annotated grid of the first attribute's predictions (uint8 on the device): predictions, confidences and the tile order are derived
-    from the device table (``grid_inputs``), the painting is one launch of ``ops.eval_grid``."""
+    from the device table (``grid_inputs``), the painting is one launch of ``ops.eval_grid``; ``labels`` as in ``device_grid_attrs``."""
     from . import ops
     k0 = tr.attrs[0][2]
     preds, maxprob, order = grid_inputs(pd, k0)
     palette = torch.tensor(PALETTE_GENDER if k0 == 2 else PALETTE_RACE, dtype=torch.uint8, device=images.device)
-    return ops.eval_grid(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, maxprob, palette)
+    grid = ops.eval_grid(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, maxprob, palette)
+    return draw_labels(grid, order, labels, images.shape[2], images.shape[3], 1)
 
 
 def _json_safe(v):
@@ -353,7 +463,7 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
     NaN (no valid row) is written as null.  With ``mode="grids"`` rank 0 also writes
     ``eval_{name}_{step}_{prompt}_{ori|generated}.jpg`` showing the first attribute; with ``"grids_attrs"`` the grids of exp-3/4/5 carry one strip
     per attribute (``device_grid_attrs``; the other experiments' files are the same in both modes); with ``"metrics"`` the frozen pass, which only
-    feeds its grid, is not generated."""
+    feeds its grid, is not generated.  A trainer that carries ``index_labels`` (``--index_font``) gets the index text on every grid."""
     from . import ops
     tr = trainer
     logs = []
@@ -382,7 +492,7 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
                 if tr.rank == 0:
                     from PIL import Image
                     os.makedirs(imgs_dir, exist_ok=True)
-                    grid = painter(tr, images_all, boxes_all, pd).cpu().numpy()
+                    grid = painter(tr, images_all, boxes_all, pd, labels=getattr(tr, "index_labels", None)).cpu().numpy()
                     Image.fromarray(grid).save(os.path.join(imgs_dir, f"eval_{name}_{step}_{prompt}_{tag}.jpg"), quality=25)
     if tr.rank == 0 and log is not None:
         keys = list(logs[0].keys()) if logs else []

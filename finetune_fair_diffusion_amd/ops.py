@@ -880,6 +880,25 @@ def eval_grid_attrs_img(images, order, boxes, preds, bar_rows, palette, rows=Non
     return out
 
 
+def eval_grid_labels(grid, order, masks, desc, H, W, n_strip, xy=(400, 400)):
+    """The reference's index text on a grid one of the three painters above has written, in place and in one launch (``fd_eval_grid_labels_u8``):
+    grid [rows*(H+20), cols*(W+50*n_strip+20), 3] uint8, order [N] int32 (tile -> image: the number printed), masks [bytes] uint8 and desc
+    [n_labels,5] int32 = (w, h, off_x, off_y, byte_offset) of ``evaluation.IndexLabels.atlas``, all on the device.  Returns ``grid``."""
+    N = order.shape[0]
+    shape = tuple(grid.shape)
+    assert grid.dtype == torch.uint8 and grid.is_cuda and grid.is_contiguous() and len(shape) == 3 and shape[2] == 3, (grid.dtype, grid.shape)
+    tw, th = W + 50 * n_strip + 20, H + 20
+    assert shape[0] % th == 0 and shape[1] % tw == 0, (shape, H, W, n_strip)      # the entry point cannot see the size of the buffer it writes into
+    rows, cols = shape[0] // th, shape[1] // tw
+    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), (order.dtype, order.shape)
+    assert masks.dtype == torch.uint8 and masks.dim() == 1 and masks.is_contiguous(), (masks.dtype, masks.shape)
+    assert desc.dtype == torch.int32 and desc.dim() == 2 and desc.shape[1] == 5 and desc.is_contiguous(), (desc.dtype, desc.shape)
+    assert order.device == masks.device == desc.device == grid.device, (grid.device, order.device, masks.device, desc.device)
+    _call("fd_eval_grid_labels_u8", _p(grid), _p(order), _p(masks), masks.numel(), _p(desc), desc.shape[0], N, H, W, n_strip, rows, cols, int(xy[0]), int(xy[1]),
+          _stream())
+    return grid
+
+
 # ----------------------------------------------------------------------------- text-encoder attention
 def small_attn_fwd(q, k, v, key_valid, B, H, T, d, scale, causal=True, save_p=False):
     o = torch.empty_like(q)

@@ -275,6 +275,8 @@ class FairnessTrainer:
         self.monitor = "off"
         self.monitor_plot = False
         self.last_monitor = self._mon = None
+        # ``evaluation.IndexLabels`` (--index_font; train.py sets it): the index text on the validation grids and the train plots.  None: no text.
+        self.index_labels = None
         if self.enumerated_targets:      # the table of the usual global face count (every image has a face); other counts are built on the worker
             composition_table(world_size * getattr(args, "train_images_per_prompt_GPU", 0))
 
@@ -699,7 +701,8 @@ class FairnessTrainer:
         producers of ``images`` and of ``classify_begin``'s handle ``h``; nothing is read back here and no random number is drawn.  The [B, sum k]
         probability table is gathered in rank order; with ``tally`` one ``ops.eval_tally`` launch reduces it to the 32 counts of
         ``evaluation.gap_metrics`` and they start their way to pinned memory.  On a plot step images and boxes are gathered too (every rank takes
-        part, as in the reference) and rank 0 paints the grid in one launch (``evaluation.device_grid_attrs``), which follows the counts."""
+        part, as in the reference) and rank 0 paints the grid in one launch (``evaluation.device_grid_attrs``), which follows the counts; with
+        ``index_labels`` one more launch on the same stream draws the index text."""
         from . import evaluation as EV
         mon = self._mon
         plot = self.monitor == "plots" and self.monitor_plot
@@ -715,7 +718,7 @@ class FairnessTrainer:
             boxes_all = EV._gather_dev(self, bx.to(self.device) if bx.is_cuda else _h2d(bx, self.device))
             mon["images"][tag], mon["boxes"][tag] = images_all, boxes_all
             if self.rank == 0:
-                mon["grids"][tag] = self._to_pinned(EV.device_grid_attrs(self, images_all, boxes_all, pd))
+                mon["grids"][tag] = self._to_pinned(EV.device_grid_attrs(self, images_all, boxes_all, pd, labels=self.index_labels))
         mon["event"] = torch.cuda.Event()
         mon["event"].record()
 

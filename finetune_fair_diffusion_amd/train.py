@@ -18,6 +18,8 @@ The training monitor is opt-in as well: ``--train_monitor metrics`` adds the ref
 (``train_gender_gap``, ``train_race_gap``, ... of the gathered probability table the finetuned model's images were classified into, tallied on the
 device; ``num_faces`` / ``num_faces_total``), ``--train_monitor plots`` also writes the reference's train plots
 ``<output_dir>/imgs/train-{global_step}_generated.jpg`` / ``_ori.jpg`` on the steps the reference writes them (``train_plot_number``).
+``--index_font PATH|default`` prints each image's index on its tile of the validation grids and the train plots, as the reference does with its
+Arial Bold file (``evaluation.IndexLabels``); without it no text is drawn.
 """
 import json
 import math
@@ -225,6 +227,9 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
         from . import evaluation
         prompts_val = evaluation.validation_prompts(_occupation_data(args))
     monitor = trainer.monitor = getattr(args, "train_monitor", "off")
+    if getattr(args, "index_font", None) and (validation in ("grids", "grids_attrs") or monitor == "plots"):
+        from .evaluation import IndexLabels
+        trainer.index_labels = IndexLabels(args.index_font, getattr(args, "index_font_size", 100))      # refuses a missing font before the first step
 
     def draw_val():
         return evaluation.draw_val_noise(len(prompts_val), args.val_images_per_prompt_GPU, lat)

@@ -387,6 +387,20 @@ int fd_eval_grid_attrs_u8(const uint8_t* images, const int32_t* order, const int
 int fd_eval_grid_attrs(const void* images, const int32_t* order, const int32_t* boxes, const int32_t* preds, const int32_t* bar_rows,
                        const uint8_t* palette, uint8_t* grid, int N, int H, int W, int n_attr, int rows, int cols, void* stream);
 
+/* ---- index labels of the annotated grids (evaluation.IndexLabels; ``img_pil_draw.text((400, 400), f"{idx.item()}", font=fnt)`` in plot_in_grid :199-200,
+ * plot_in_grid_gender_race[_age] and eval-generated-images.py :150-151, :245-246).  Additive: FD_ABI_VERSION is unchanged.
+ * An in-place pass over a grid [rows*(H+20), cols*(W+50*n_strip+20), 3] uint8 already painted by fd_eval_grid_u8 (n_strip = 1), fd_eval_grid_attrs_u8 or
+ * fd_eval_grid_attrs (n_strip = n_attr), one launch for all tiles.  Tile t shows image i = order[t] and gets label i: the 8-bit coverage mask of the
+ * string str(i), w x h bytes row-major at masks + byte_offset, where desc [n_labels,5] int32 = (w, h, off_x, off_y, byte_offset) per label.  Its top-left
+ * lies at (x + off_x, y + off_y) of the tile's inner area (W+50*n_strip by H, inside the 10-pixel frame); every mask byte m that falls inside that area
+ * updates the three channels a of its pixel with white ink by PIL's rule t = a*(255-m) + 255*m + 128, a' = ((t >> 8) + t) >> 8 (m = 0: identity); the
+ * rest is clipped, so frame and neighbouring tiles are never touched.  Tiles past N and tiles whose order entry is outside [0,N) get nothing.  order [N]
+ * int32, masks [mask_bytes] uint8 and desc are on the device; the table is checked per tile ON the device: a label index outside [0,n_labels), w <= 0,
+ * h <= 0, byte_offset < 0 or byte_offset + w*h > mask_bytes draws nothing for that tile and reads no mask byte.  Refused on the host: null pointers,
+ * N, H, W outside 1..4096, n_strip outside 1..FD_EVAL_MAX_ATTR, a rows x cols that is not the painters', n_labels < 1, mask_bytes < 0. */
+int fd_eval_grid_labels_u8(uint8_t* grid, const int32_t* order, const uint8_t* masks, int64_t mask_bytes, const int32_t* desc, int n_labels, int N, int H,
+                           int W, int n_strip, int rows, int cols, int x, int y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
