@@ -20,12 +20,18 @@ encoders are attached (``clip_model`` / ``dino_model``, vit.py), plus ``weight_l
 face-feature network and its feature database are attached (``face_net`` sfnet.py, ``face_db``); all input gradients join the
 classifier's at the image and go through the VAE once.  A non-zero ``weight_loss_face`` without a face network is refused
 rather than silently dropped.
+
+``FairnessTrainer.train_step`` is the list of the step's phases and owns every phase mark; each phase is one method right below it, and data
+crosses phases as return values or in the per-step record ``st`` (``_step_record``).  The device tail (exp-1 / exp-2: targets, loss, weights
+and hook factors on the device, ONE read-back per step) and the host tail (exp-3..6, FD_HOST_TAIL=1) sit side by side inside each phase.
 """
 import contextlib
-import math
+import copy
 import os
 import threading
 import time
+from functools import partial
+from types import SimpleNamespace
 
 import torch
 import torch.distributed as dist
@@ -39,11 +45,9 @@ from . import fairness_dev as FD
 from . import unet as unet_mod
 from .layers import F16, F32
 from .lr_schedule import lr_lambda
+from .sfnet import face_features, face_features_backward
 from .vit import feature_loss_and_grad
 
-# The two halves of a CFG batch share everything up to the first cross-attention (unet.forward_step(pair=True)); FD_NO_CFG_PAIR=1
-# evaluates the duplicated batch instead (A/B measurement only; eps is bit-identical either way).
-_CFG_PAIR = os.environ.get("FD_NO_CFG_PAIR") is None
 _ROCTX = os.environ.get("FD_ROCTX") is not None
 
 
@@ -101,35 +105,25 @@ def _all_tensors(obj, out=None):
     return out
 
 
-def _pow2_scale(amax, target):
-    if not math.isfinite(amax) or amax <= 0:
-        return 1.0
-    return float(2.0 ** round(math.log2(target / amax)))
-
-
 def _pow2_scale_dev(amax, target):
-    """``_pow2_scale`` evaluated ON THE DEVICE (``amax``: device tensor of any shape -> same-shape fp32 power of two, 1 where amax is 0 or not
-    finite): the loss scales of the VAE / ViT / SFNet / U-Net backwards no longer bounce through the host, so the tail of the step has no
-    read-back between the two logits copies and the end of the step (FD_HOST_SCALES=1 restores the four host syncs for A/B)."""
+    """The power of two nearest to ``target / amax``, chosen ON THE DEVICE (``amax``: device tensor of any shape -> same-shape fp32, 1 where amax
+    is 0 or not finite): the loss scales of the VAE / ViT / SFNet / U-Net backwards do not bounce through the host, so the tail of the step has no
+    read-back between the two logits copies and the end of the step."""
     a = amax.float()
     ok = torch.isfinite(a) & (a > 0)
     s = torch.exp2(torch.round(torch.log2(target / torch.where(ok, a, torch.ones_like(a)))))
     return torch.where(ok, s, torch.ones_like(s))
 
 
-_HOST_SCALES = os.environ.get("FD_HOST_SCALES") is not None
+def _scaled_backward(backward, grad, scale, unscale=1.0):
+    """The device loss-scale idiom of every backward in the tail: the gradient enters multiplied by the power-of-two ``scale`` with gscale = 1;
+    returns (result, unscale / scale) -- the caller multiplies by that exact inverse (a power-of-two multiply commutes with every rounding)."""
+    return backward(grad * scale, 1.0), unscale / scale
+
+
 # FD_HOST_TAIL=1 (A/B): exp-1's targets / loss assembly on the HOST as in rounds 1-3 (two logits read-backs in the tail); default: on the device
 _HOST_TAIL = os.environ.get("FD_HOST_TAIL") is not None
-_R2_SIDE_OLD = os.environ.get("FD_R2_SIDE_HOST_ORDER") is not None
-# FD_ATOMIC_DKDV=1 (A/B): shared cross-attention dK / dV accumulated with fp32 atomics across samples, timesteps and streams, as in rounds 1-3
-_ATOMIC_DKDV = os.environ.get("FD_ATOMIC_DKDV") is not None
-_NO_PINNED_H2D = os.environ.get("FD_NO_PINNED_H2D") is not None
 _FINE_MARKS = os.environ.get("FD_FINE_MARKS") is not None
-_MAIN_PRIORITY = int(os.environ.get("FD_MAIN_PRIORITY", "0"))
-# FD_TAIL_REORDER=1 (measurement): enqueue the recorded CLIP / DINO forward of R1's images and R2's feature encoders AHEAD of the logits' read-backs.
-# Measured slower (1409-1424 vs 1378-1402 ms, profiles/r03_step_ab_tail_reorder_rejected.txt): the work it moves in front of the first read-back
-# delays everything behind it by its full device time, while in the old order it hides behind the host-paced loss phase.
-_NO_TAIL_REORDER = os.environ.get("FD_TAIL_REORDER") is None
 
 
 def _h2d(t, dev):
@@ -137,8 +131,6 @@ def _h2d(t, dev):
     non-blocking; ``t.to(dev)`` from pageable memory is a synchronous hipMemcpy behind everything queued on the launch stream.  The loss
     phase has nine such copies between its read-backs (loss phase 62-78 -> 55-58 ms; the whole step within noise,
     profiles/r03_step_ab_pinned_h2d.txt)."""
-    if _NO_PINNED_H2D:          # measurement switch (FD_NO_PINNED_H2D=1): the old pageable copies
-        return t.to(dev).contiguous()
     return t.contiguous().pin_memory().to(dev, non_blocking=True)
 
 
@@ -240,6 +232,9 @@ class FairnessTrainer:
         self.concurrent_bwd = os.environ.get("FD_NO_CONCURRENT_BWD") is None
         self.bwd_streams = int(os.environ.get("FD_BWD_STREAMS", "3"))     # measured: 2 -> 1647, 3 -> 1589, 4 -> 1633 ms per step (run-to-run noise ~2 %)
         self._side = None
+        # ``_usable_free_bytes``: calls and allocator-snapshot walks so far, ``memory_reserved`` at the last walk, the side streams' share found by it
+        self._snap_calls = self._snap_walks = self._other_stream_cache = 0
+        self._snap_reserved = -1
         # race-detector knobs (tests / scratch/diag_hazard.py; never set by the product): ``bwd_virtual`` deals the timesteps to the same per-stream
         # gradient buffers but enqueues all of them on the launch stream -- same fp32 summation order as the concurrent schedule, so every
         # buffer must come out BIT-identical; ``bwd_keep_alive`` holds every consumed activation context until the backward has been joined;
@@ -255,9 +250,6 @@ class FairnessTrainer:
         # profiles/r05_step_ab_schedule_knobs_final_tree.txt): 0 -> 1317-1326, 2 -> 1309-1310, 4 -> 1307-1310, 5 -> 1309-1315, 6 -> 1309-1313, 7 -> 1315-1320, 8 -> 1316-1320,
         # 10 -> 1323-1325, 12 -> 1334-1338: the flat region moved down as the tail got shorter; 5 sits in its middle
         self.r2_prefetch_steps = int(os.environ.get("FD_R2_PREFETCH_STEPS", "5"))
-        # ... and ``r2_prefetch_late`` more of them are enqueued behind the U-Net backward's last timestep: they run while the backward streams
-        # drain unevenly, through the optimiser step and under the first (host-paced) forward of the next step
-        self.r2_prefetch_late = int(os.environ.get("FD_R2_PREFETCH_LATE", "0"))
         # the frozen model's forward (R2: a third of the step's U-Net passes) replayed as a hipGraph: bit-identical to the eager forward, ~2900 C-ABI
         # calls per forward become one launch -- the enqueue thread keeps a larger lead over the device in the rollout phase, where its lead is smallest
         # (fewer of the +50..95 ms steps, median -5..-15 ms in 20-step runs: profiles/r04_step_jitter_r2_graph.txt).  FD_R2_GRAPH=0 turns it off.
@@ -320,9 +312,7 @@ class FairnessTrainer:
         if self._side is None:
             self._side = {}
         if k not in self._side:
-            # FD_R2_PRIORITY (measurement): HIP priority of the frozen-model rollout's stream (-1 high, 0 normal, 1 low where the runtime has it)
-            prio = int(os.environ.get("FD_R2_PRIORITY", "0")) if k == "r2" else 0
-            self._side[k] = torch.cuda.Stream(device=self.device, priority=prio) if prio else torch.cuda.Stream(device=self.device)
+            self._side[k] = torch.cuda.Stream(device=self.device)
         return self._side[k]
 
     # ------------------------------------------------------------------ pieces
@@ -341,7 +331,7 @@ class FairnessTrainer:
         (288 GB holds the whole 20-step chain at batch 8); the remaining steps are recomputed in the backward."""
         sch = self.sch if sch is None else sch       # a prefetched R2 rollout of the NEXT step brings its own scheduler object (S may differ)
         graphed = None
-        if (self.r2_graph and unet is self.eval_unet and unet is not self.unet and unet.lora_bank is None and _CFG_PAIR
+        if (self.r2_graph and unet is self.eval_unet and unet is not self.unet and unet.lora_bank is None
                 and not keep_inputs and not keep_activations and not record_prompt and torch.cuda.current_stream() != torch.cuda.default_stream()):
             graphed = getattr(unet, "graphed", None) or unet_mod.GraphedForward(unet)
         sch.set_timesteps(S)
@@ -374,12 +364,12 @@ class FairnessTrainer:
                 inputs.append(lat.clone())
             rec = keep_activations and (i == 0 or budget > 0)
             if graphed is not None:        # the frozen model's non-recording forward as ONE hipGraph launch (unet.GraphedForward)
-                eps = graphed(lat, i, _CFG_PAIR)
+                eps = graphed(lat, i, True)
                 sch.cfg_step(i, eps, gs, lat, state)
                 yield i
                 continue
-            x = ops.to_f16(lat)
-            eps = unet.forward_step(x if _CFG_PAIR else x.repeat(2, 1, 1, 1), i, record=rec, pair=_CFG_PAIR)   # cat([latents] * 2) (:1043)
+            # cat([latents] * 2) (:1043): the two halves of the CFG batch share everything up to the first cross-attention (unet.forward_step(pair=True))
+            eps = unet.forward_step(ops.to_f16(lat), i, record=rec, pair=True)
             if rec:
                 ctxs[i] = unet._ctx
                 unet._ctx = None
@@ -410,16 +400,16 @@ class FairnessTrainer:
         free, _ = torch.cuda.mem_get_info()
         cached = torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
         cur = torch.cuda.current_stream().cuda_stream
-        n = getattr(self, "_snap_calls", 0)
+        n = self._snap_calls
         self._snap_calls = n + 1
         reserved = torch.cuda.memory_reserved()
-        grown = abs(reserved - getattr(self, "_snap_reserved", -1)) > (1 << 30)      # the pools moved by > 1 GiB since the last walk (a new S / batch,
+        grown = abs(reserved - self._snap_reserved) > (1 << 30)      # the pools moved by > 1 GiB since the last walk (a new S / batch,
                                                                                       # fragmentation in a long run): the side-stream share is stale
         if n < 2 or n % 256 == 0 or grown:
             # the pools settle within two steps; the snapshot walks every block of the allocator (tens of ms of host time at 175 GB) right at
             # the start of a step, where the device queue is empty: refreshed rarely -- and whenever ``memory_reserved`` has moved
             self._snap_reserved = reserved
-            self._snap_walks = getattr(self, "_snap_walks", 0) + 1
+            self._snap_walks += 1
             other = 0
             try:
                 for seg in torch.cuda.memory_snapshot():
@@ -484,19 +474,23 @@ class FairnessTrainer:
         """Classifier forward and regulariser features of the frozen side's images, enqueued on the CURRENT (R2) stream; the tensors are handed to
         ``consumer`` (the launch stream waits on the event recorded behind them)."""
         r = dict(h_o=self.classify_begin(images_ori))
+        r.update(self._ori_features(images_ori, r["h_o"]["ind"], B))
+        for t in (r["h_o"]["logits_dev"], r.get("clip_ori"), r.get("dino_ori"), r.get("face_ori")):
+            if t is not None:
+                t.record_stream(consumer)
+        return r
+
+    def _ori_features(self, images_ori, ind_o, B):
+        """Regulariser features of the frozen side's images: normalised CLIP / DINOv2 embeddings and, per image with a face, its face features."""
+        r = {}
         if self.use_img_loss:                                                    # :1860-1862
             e_co, e_do = self.image_features(self.resize_small(images_ori)[0])
             r.update(clip_ori=F.normalize(e_co, dim=-1), dino_ori=F.normalize(e_do, dim=-1))
         if self.use_face_loss:                                                   # :1870
-            from .sfnet import face_features
-            ch_o, idx_o, _ = self.aligned_faces(images_ori, r["h_o"]["ind"])
-            face_ori = torch.zeros((B, 512), dtype=F32, device=self.device)
+            ch_o, idx_o, _ = self.aligned_faces(images_ori, ind_o)
+            r["face_ori"] = torch.zeros((B, 512), dtype=F32, device=self.device)
             if len(idx_o):
-                face_ori[idx_o.long()] = F.normalize(face_features(self.face_net, ch_o)[0], dim=-1)
-            r["face_ori"] = face_ori
-        for t in (r["h_o"]["logits_dev"], r.get("clip_ori"), r.get("dino_ori"), r.get("face_ori")):
-            if t is not None:
-                t.record_stream(consumer)
+                r["face_ori"][idx_o.long()] = F.normalize(face_features(self.face_net, ch_o)[0], dim=-1)
         return r
 
     def classify_dev(self, h):
@@ -510,6 +504,10 @@ class FairnessTrainer:
         else:
             probs, preds, lg = FD.probs_preds(logits_dev, _h2d(sel, self.device), N, c0, k)
         return ind, boxes, [dict(name=name, preds=preds, probs=probs, logits=lg, ind_dev=_h2d(ind, self.device))]
+
+    def _classify_read(self, h):
+        """Per-attribute tensors of a ``classify_begin`` handle where this trainer's tail wants them: on the device, or read back to the host."""
+        return self.classify_dev(h) if self.device_tail else self.classify_end(h)
 
     def _binom_tables(self, n):
         if n not in self._binom:
@@ -728,436 +726,421 @@ class FairnessTrainer:
             for bank in self.banks:
                 dist.all_reduce(bank.grad, op=dist.ReduceOp.SUM)
 
-    # ------------------------------------------------------------------ the step
+    # ------------------------------------------------------------------ the step: ``train_step`` lists the phases and owns every phase mark; the phases follow it
     def train_step(self, tokens, noises, S, tokens_ori=None, next_step=None):
-        """One training step (``_train_step`` below).  With FD_MAIN_PRIORITY=-1 (measurement) the whole step is launched from a HIGH-priority stream
-        instead of the caller's current one, so that the critical path's many small tail kernels are dispatched ahead of the frozen-model
-        rollout's (normal-priority) kernels they share the chip with."""
-        if _MAIN_PRIORITY == 0:
-            return self._train_step(tokens, noises, S, tokens_ori, next_step)
-        if getattr(self, "_main_stream", None) is None:
-            self._main_stream = torch.cuda.Stream(device=self.device, priority=_MAIN_PRIORITY)
-        caller = torch.cuda.current_stream()
-        self._main_stream.wait_stream(caller)
-        with torch.cuda.stream(self._main_stream):
-            out = self._train_step(tokens, noises, S, tokens_ori, next_step)
-        caller.wait_stream(self._main_stream)
-        return out
-
-    def _train_step(self, tokens, noises, S, tokens_ori=None, next_step=None):
         """``tokens``: the prompt the finetuned side sees (exp-2: ``prompt_debiaser(prompt)``, generate.prefix_tokens); ``tokens_ori``: the
         prompt of the frozen original side R2 when it differs (exp-2 :1954: the plain prompt, no prefix embedding).
         ``next_step``: optional dict(tokens_ori=, noises=, S=) -- the inputs the NEXT call will receive (noises as a host tensor): the first
-        ``r2_prefetch_steps`` denoising steps of its R2 rollout are then enqueued underneath this step's tail."""
-        args = self.args
+        ``r2_prefetch_steps`` denoising steps of its R2 rollout are then enqueued underneath this step's tail.
+        The phases below are called in enqueue order: what is queued on which stream in which order is part of the result and of the speed."""
         tokens_ori = tokens if tokens_ori is None else tokens_ori
-        dev = self.device
-        B = noises.shape[0]
+        pre, noises = self._begin_step(tokens_ori, noises, S)
+        self._mark("R1_rollout")
+        st = self._step_record(tokens, tokens_ori, noises, S)
+        out, dv = st.out, self.device_tail
+        # ---- R1: images from the model being finetuned (:1786-1795); with ``st.conc`` R2 (frozen original, :1844-1858) runs beside it on its own stream
+        g2, r2 = self._r2_start(st, pre)
+        enc, r1s = self._r1_rollouts(st, g2)
+        self._mark("R1_vae")
+        images = self.decode(r1s[0]["lat"], record=True) if st.share else torch.cat([self.decode(r["lat"]) for r in r1s])
+        if st.conc:
+            images_ori, r2side, ev_r2 = self._r2_finish_on_side(st, g2, r2)
+            self._prefetch_next_r2(st, next_step)       # queued behind ``ev_r2``: the launch stream never waits for a prefetch
+        self._mark("classify_targets")
+        gen = self._classify_generated(st, images)      # logits read-back (host tail), then the dynamic targets' solve starts underneath R2
+        if st.conc:             # ---- R2: images from the frozen original models (:1844-1858)
+            self._mark("R2_tail_and_regularisers")
+            st.cur.wait_event(ev_r2)              # everything downstream (classifier, feature encoders, loss) consumes images_ori on ``cur``
+            images_ori.record_stream(st.cur)
+        else:
+            self._mark("R2_rollout")
+            enc_ori = self.encode_pair(self.eval_te, tokens_ori) if (self.eval_te is not self.te or st.train_prefix or tokens_ori is not tokens) else enc
+            lats = [self.rollout(self.eval_unet, enc_ori, noises[j:j + st.vb], S)[0] for j in range(0, st.B, st.vb)]
+            self._mark("R2_vae")
+            images_ori, r2side = torch.cat([self.decode(x) for x in lats]), None
+            self._mark("R2_classify_regularisers")
+        ori = self._r2_complete(st, images_ori, r2side)
+        tgt = self._targets(st, gen["per"])
+        # ---- R3: rollout with gradient (:1889-1933), all micro-batches at once with weights 1/n_j (``st.w``)
+        if st.share:            # R1's recorded rollout / decode / classifier forward IS R3's forward (``share_r1_r3``)
+            gen.update(enc=enc, inputs=r1s[0]["inputs"], ctxs=r1s[0]["ctxs"])
+        else:
+            self._mark("R3_fwd_rollout")
+            enc_g = self.encode_pair(self.te, tokens, record=st.rec_te, prefix=st.pv)
+            x_final, inputs, ctxs = self.rollout(self.unet, enc_g, noises, S, keep_inputs=True, record_prompt=True, keep_activations=self.keep_activations)
+            self._mark("R3_fwd_vae")
+            images_g = self.decode(x_final, record=True)
+            ind_g, boxes_g, per_g = self._classify_read(self.classify_begin(images_g, record=True))
+            gen = dict(images=images_g, ind=ind_g, boxes=boxes_g, per=per_g, enc=enc_g, inputs=inputs, ctxs=ctxs)
+        self._mark("R3_loss_and_image_grad")
+        st.w_dev = _h2d(st.w, self.device) if dv else None
+        dlog_full = self._fair_loss(st, gen, tgt)
+        d_img = self._image_term(st, gen, ori, tgt) if self.use_img_loss else None
+        d_img = self._face_term(st, gen, ori, tgt, d_img) if self.use_face_loss else d_img
+        d_img = self._classifier_backward(st, gen, dlog_full, d_img)
+        if d_img is not None:
+            self._mark("R3_bwd_vae")
+            g, step_scale, inv_gscale = self._vae_backward(st, d_img)
+            self._mark("R3_bwd_unet")
+            if st.train_unet or st.train_te or st.train_prefix:
+                self._unet_backward(st, gen, g, step_scale, inv_gscale)
+        else:
+            self.vae._ctx = None
+        gen["ctxs"].clear()
+        for fn in st.deferred:      # the host tail's read-backs of reported values: only now, with the whole backward enqueued
+            fn()
+        self._mark("sync_update")       # ---- gradient sync, guard, update (:1998-2029)
+        self._sync_and_report(st)
+        self._mark("end")
+        return out
+
+    def _begin_step(self, tokens_ori, noises, S):
+        """Takes the R2 rollout a previous step prefetched for these very inputs -- or drops it -- and moves the noise to the device; resets what the
+        step accumulates (LoRA gradients, monitor, marks).  Returns (prefetch record or None, device noises)."""
         pre, self._r2_pre = self._r2_pre, None
         if pre is not None and not (pre["S"] == S and not noises.is_cuda and pre["noises_host"].shape == noises.shape and
                                     torch.equal(pre["noises_host"], noises.to(F32)) and
                                     all(torch.equal(a, b) for a, b in zip(pre["tokens_ori"], tokens_ori))):
             pre = None              # the caller changed its mind: the prefetched steps are dropped (their kernels were harmless)
-        if pre is not None:
+        if pre is not None:         # the noise went up on the R2 stream: wait for it, and tell the allocator, BEFORE anything uses ``noises``
             torch.cuda.current_stream().wait_event(pre["ev_noise"])
             noises = pre["noises_dev"]
             noises.record_stream(torch.cuda.current_stream())
         else:
-            noises = noises.to(dev, F32)
-        out = {}
+            noises = noises.to(self.device, F32)
         self.last_monitor = None
-        mon = self._mon = dict(tables={}, images={}, boxes={}, grids={}) if self.monitor != "off" else None
+        self._mon = dict(tables={}, images={}, boxes={}, grids={}) if self.monitor != "off" else None
         for bank in self.banks:
             bank.grad.zero_()
-        vb = args.val_GPU_batch_size
         self._marks, self._host_marks = [], []
-        self._mark("R1_rollout")
-        # ---- R1: images from the model being finetuned (:1786-1795)
+        return pre, noises
+
+    def _step_record(self, tokens, tokens_ori, noises, S):
+        """What every phase of one step needs to know: its inputs, what is trained, the schedule chosen for it, the micro-batch weights, and the
+        three collectors -- ``out`` (the caller's dict), ``rb`` (device tail: name -> device tensor, read back ONCE at the end) and ``deferred``."""
+        args, B, vb = self.args, noises.shape[0], self.args.val_GPU_batch_size
         train_te = getattr(args, "train_text_encoder", False) and self.te.lora_bank is not None
         train_unet = getattr(args, "train_unet", False) and self.unet.lora_bank is not None
         train_prefix = self.prefix is not None
-        pv = self.prefix.vectors() if train_prefix else None
-        rec_te = train_te or train_prefix
         share = self.share_r1_r3 and vb >= B and self.eval_unet is not self.unet and (train_unet or train_te or train_prefix)
-        shared = None
         # R1 (finetuned model) and R2 (frozen original, :1844-1858) are independent until the loss: with ``concurrent_r2`` their denoising
         # steps are enqueued in lockstep on two HIP streams, so the many launches that cannot fill 256 CUs on their own (16x16 / 8x8 levels,
         # tail waves, latency-bound short-K GEMMs) overlap with the other rollout's work.  Same kernels, same results.
         conc = self.concurrent_r2 and vb >= B and self.eval_unet is not self.unet
-        cur = torch.cuda.current_stream()
-        side = self._side_stream("r2") if conc else None      # its own stream: the backward's side streams must not queue behind a prefetch
-        r2 = {}
+        w, N_backward = microbatch_weights(B, args.train_GPU_batch_size)
+        return SimpleNamespace(tokens=tokens, tokens_ori=tokens_ori, noises=noises, S=S, B=B, vb=vb, train_te=train_te, train_unet=train_unet,
+                               train_prefix=train_prefix, pv=self.prefix.vectors() if train_prefix else None, rec_te=train_te or train_prefix,
+                               share=share, conc=conc, cur=torch.cuda.current_stream(),
+                               side=self._side_stream("r2") if conc else None,      # its own stream: the backward's side streams must not queue behind a prefetch
+                               w=w, w_dev=None, N_backward=N_backward, out={}, rb={}, deferred=[])
+
+    def _r2_start(self, st, pre):
+        """The concurrent R2 rollout as a generator on the R2 stream -- the prefetched one, already ``pre["k"]`` denoising steps ahead, or a new one."""
         self.last_r2_prefetched = 0
-        if conc and pre is not None:
-            g2, r2 = pre["gen"], pre["res"]                       # already ``pre["k"]`` denoising steps ahead
+        if not st.conc:
+            return None, {}
+        if pre is not None:
             self.last_r2_prefetched = pre["k"]
-        elif conc:
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                enc_ori = self.encode_pair(self.eval_te, tokens_ori)
-                g2 = self.rollout_steps(self.eval_unet, enc_ori, noises, S, r2)
-        if share:
-            enc = self.encode_pair(self.te, tokens, record=rec_te, prefix=pv)
-            r1 = {}
-            g1 = self.rollout_steps(self.unet, enc, noises, S, r1, keep_inputs=True, record_prompt=True, keep_activations=self.keep_activations)
+            return pre["gen"], pre["res"]
+        r2 = {}
+        st.side.wait_stream(st.cur)
+        with torch.cuda.stream(st.side):
+            return self.rollout_steps(self.eval_unet, self.encode_pair(self.eval_te, st.tokens_ori), st.noises, st.S, r2), r2
+
+    def _r1_rollouts(self, st, g2):
+        """R1's denoising rollout(s): one recording rollout that R3 consumes (``st.share``) or plain ones in ``val_GPU_batch_size`` chunks.  One R2
+        denoising step is enqueued on the R2 stream after each R1 step's launches.  Returns (enc, [rollout result per chunk])."""
+        def lockstep(g1):
             for _ in g1:
-                if conc:
-                    with torch.cuda.stream(side):
+                if st.conc:
+                    with torch.cuda.stream(st.side):
                         next(g2, None)
-            x_final, inputs, ctxs = r1["lat"], r1["inputs"], r1["ctxs"]
-            self._mark("R1_vae")
-            images = self.decode(x_final, record=True)
-            shared = (enc, inputs, ctxs)
+        if st.share:
+            enc, r1s = self.encode_pair(self.te, st.tokens, record=st.rec_te, prefix=st.pv), [{}]
+            lockstep(self.rollout_steps(self.unet, enc, st.noises, st.S, r1s[0], keep_inputs=True, record_prompt=True, keep_activations=self.keep_activations))
         else:
-            enc = self.encode_pair(self.te, tokens, prefix=pv)
-            lats = []
-            for j in range(0, B, vb):
-                r1 = {}
-                for _ in self.rollout_steps(self.unet, enc, noises[j:j + vb], S, r1):
-                    if conc:
-                        with torch.cuda.stream(side):
-                            next(g2, None)
-                lats.append(r1["lat"])
-            self._mark("R1_vae")
-            images = torch.cat([self.decode(x) for x in lats])
-        if conc:
-            with torch.cuda.stream(side):
-                for _ in g2:           # (nothing left when both rollouts have S steps)
-                    pass
-                images_ori = self.decode(r2["lat"])
-                # the frozen side's classifier and regulariser forwards (:1860-1870) depend on images_ori only: enqueued HERE, on the R2 stream, they run
-                # beside R1's last denoising steps instead of on the launch stream between R1's classifier and the loss (FD_R2_SIDE_HOST_ORDER=1: as before)
-                r2side = None
-                if not _R2_SIDE_OLD:
-                    r2side = self._r2_side_forwards(images_ori, B, cur)
-            ev_r2 = torch.cuda.Event()
-            ev_r2.record(side)         # what the main stream waits for below: this step's R2, not a prefetch queued behind it
-            can_prefetch = (next_step is not None and self.r2_prefetch_steps > 0 and not next_step["noises"].is_cuda and
-                            next_step["noises"].shape[0] <= vb and not (train_te and self.eval_te is self.te))
-            if can_prefetch:
-                import copy
-                if self._sch_r2 is None:
-                    self._sch_r2 = copy.deepcopy(self.sch)
-                nt = next_step.get("tokens_ori")
-                k = min(self.r2_prefetch_steps, int(next_step["S"]))
-                with torch.cuda.stream(side):
-                    nh = next_step["noises"].to(F32)
-                    nd = nh.to(dev, non_blocking=False)
-                    ev_noise = torch.cuda.Event()
-                    ev_noise.record(side)
-                    r2n = {}
-                    g2n = self.rollout_steps(self.eval_unet, self.encode_pair(self.eval_te, nt), nd, int(next_step["S"]), r2n, sch=self._sch_r2)
-                    for _ in range(k):
-                        next(g2n, None)
-                self._r2_pre = dict(gen=g2n, res=r2n, k=k, S=int(next_step["S"]), noises_host=nh.clone(), noises_dev=nd, ev_noise=ev_noise,
-                                    tokens_ori=tuple(t.clone() for t in nt))
-        self._mark("classify_targets")
-        # (FD_TAIL_REORDER=1 enqueues the recorded CLIP / DINO forward of the loss here, ahead of the tail's first read-back: measured slower)
-        h_g = self.classify_begin(images, record=share)
-        pre_g = None
-        if share and self.use_img_loss and not _NO_TAIL_REORDER:
-            small_g, fullbox_g = self.resize_small(images)
-            pre_g = (fullbox_g,) + tuple(self.image_features(small_g, record=True))
-        dv = self.device_tail
-        rb = {}                # device_tail: what the step reports about itself, read back ONCE at the end (name -> device tensor)
-        ind, boxes, per = self.classify_dev(h_g) if dv else self.classify_end(h_g)
-        # ---- dynamic targets from the global batch (:1805-1837): gathered now, solved underneath R2, consumed by R3's loss
-        self.start_dynamic_targets(per, B)
-        out.update(images=images)
-        if mon is not None:
+            enc, r1s = self.encode_pair(self.te, st.tokens, prefix=st.pv), []
+            for j in range(0, st.B, st.vb):
+                r1s.append({})
+                lockstep(self.rollout_steps(self.unet, enc, st.noises[j:j + st.vb], st.S, r1s[-1]))
+        return enc, r1s
+
+    def _r2_finish_on_side(self, st, g2, r2):
+        """Rest of the concurrent R2 on its stream: drain, decode, the frozen side's forwards; ``ev_r2`` is what the launch stream later waits for."""
+        with torch.cuda.stream(st.side):
+            for _ in g2:           # (nothing left when both rollouts have S steps)
+                pass
+            images_ori = self.decode(r2["lat"])
+            # the frozen side's classifier and regulariser forwards (:1860-1870) depend on images_ori only: enqueued HERE, on the R2 stream, they run
+            # beside R1's last denoising steps instead of on the launch stream between R1's classifier and the loss
+            r2side = self._r2_side_forwards(images_ori, st.B, st.cur)
+        ev_r2 = torch.cuda.Event()
+        ev_r2.record(st.side)         # this step's R2, not a prefetch queued behind it
+        return images_ori, r2side, ev_r2
+
+    def _prefetch_next_r2(self, st, next_step):
+        """Enqueues the first ``r2_prefetch_steps`` denoising steps of the NEXT step's R2 on the R2 stream and leaves the rest in ``_r2_pre``."""
+        if not (next_step is not None and self.r2_prefetch_steps > 0 and not next_step["noises"].is_cuda and
+                next_step["noises"].shape[0] <= st.vb and not (st.train_te and self.eval_te is self.te)):
+            return
+        if self._sch_r2 is None:
+            self._sch_r2 = copy.deepcopy(self.sch)
+        nt, Sn = next_step.get("tokens_ori"), int(next_step["S"])
+        k = min(self.r2_prefetch_steps, Sn)
+        with torch.cuda.stream(st.side):
+            nh = next_step["noises"].to(F32)
+            nd = nh.to(self.device, non_blocking=False)
+            ev_noise = torch.cuda.Event()
+            ev_noise.record(st.side)
+            r2n = {}
+            g2n = self.rollout_steps(self.eval_unet, self.encode_pair(self.eval_te, nt), nd, Sn, r2n, sch=self._sch_r2)
+            for _ in range(k):
+                next(g2n, None)
+        self._r2_pre = dict(gen=g2n, res=r2n, k=k, S=Sn, noises_host=nh.clone(), noises_dev=nd, ev_noise=ev_noise, tokens_ori=tuple(t.clone() for t in nt))
+
+    def _classify_generated(self, st, images):
+        """R1's images through face detection and classifier; the dynamic targets of the global batch (:1805-1837) are gathered now, solved underneath
+        R2 and consumed by R3's loss.  Launch-stream order: classifier forward, logits read-back (host tail), targets, monitor."""
+        h_g = self.classify_begin(images, record=st.share)
+        ind, boxes, per = self._classify_read(h_g)
+        self.start_dynamic_targets(per, st.B)
+        st.out.update(images=images)
+        if self._mon is not None:
             self._monitor_side("generated", images, h_g, tally=True)
-        (rb if dv else out).update(probs=per[0]["probs"], preds=per[0]["preds"])
-        # ---- R2: images from the frozen original models (:1844-1858)
-        if conc:
-            self._mark("R2_tail_and_regularisers")
-            cur.wait_event(ev_r2)              # everything downstream (classifier, feature encoders, loss) consumes images_ori on ``cur``
-            images_ori.record_stream(cur)
-        else:
-            self._mark("R2_rollout")
-            enc_ori = self.encode_pair(self.eval_te, tokens_ori) if (self.eval_te is not self.te or train_prefix or tokens_ori is not tokens) else enc
-            lats = [self.rollout(self.eval_unet, enc_ori, noises[j:j + vb], S)[0] for j in range(0, B, vb)]
-            self._mark("R2_vae")
-            images_ori = torch.cat([self.decode(x) for x in lats])
-            self._mark("R2_classify_regularisers")
-        if conc and r2side is not None:
-            h_o, clip_ori, dino_ori, face_ori = r2side["h_o"], r2side.get("clip_ori"), r2side.get("dino_ori"), r2side.get("face_ori")
-            ind_o, boxes_o, per_o = self.classify_dev(h_o) if dv else self.classify_end(h_o)
+        (st.rb if self.device_tail else st.out).update(probs=per[0]["probs"], preds=per[0]["preds"])
+        return dict(images=images, ind=ind, boxes=boxes, per=per)
+
+    def _r2_complete(self, st, images_ori, r2side):
+        """What the loss needs of the frozen side, as one record.  ``r2side``: the forwards the concurrent R2 already enqueued on its stream; None
+        (sequential R2): they are enqueued here, the feature encoders after the logits' read-back."""
+        if r2side is not None:
+            h_o, feats = r2side["h_o"], r2side
+            ind_o, boxes_o, per_o = self._classify_read(h_o)
         else:
             h_o = self.classify_begin(images_ori)
-            if _NO_TAIL_REORDER:
-                ind_o, boxes_o, per_o = self.classify_dev(h_o) if dv else self.classify_end(h_o)
-            ind_o = h_o["ind"]
-            if self.use_img_loss:                                                    # :1860-1862
-                e_co, e_do = self.image_features(self.resize_small(images_ori)[0])
-                clip_ori, dino_ori = F.normalize(e_co, dim=-1), F.normalize(e_do, dim=-1)
-            if self.use_face_loss:                                                   # :1870
-                from .sfnet import face_features
-                ch_o, idx_o, _ = self.aligned_faces(images_ori, ind_o)
-                face_ori = torch.zeros((B, 512), dtype=F32, device=dev)
-                if len(idx_o):
-                    face_ori[idx_o.long()] = F.normalize(face_features(self.face_net, ch_o)[0], dim=-1)
-            if not _NO_TAIL_REORDER:                 # the read-back of R2's logits comes after its feature encoders have been enqueued
-                ind_o, boxes_o, per_o = self.classify_dev(h_o) if dv else self.classify_end(h_o)
-        out.update(images_ori=images_ori)
-        if mon is not None:
+            ind_o, boxes_o, per_o = self._classify_read(h_o)
+            feats = self._ori_features(images_ori, ind_o, st.B)
+        st.out.update(images_ori=images_ori)
+        if self._mon is not None:
             self._monitor_side("ori", images_ori, h_o, tally=False)
-        (rb if dv else out).update(preds_ori=per_o[0]["preds"], probs_ori=per_o[0]["probs"])
+        (st.rb if self.device_tail else st.out).update(preds_ori=per_o[0]["preds"], probs_ori=per_o[0]["probs"])
+        return dict(images=images_ori, h=h_o, ind=ind_o, boxes=boxes_o, per=per_o, clip=feats.get("clip_ori"), dino=feats.get("dino_ori"), face=feats.get("face_ori"))
+
+    def _targets(self, st, per):
+        """Joins the dynamic targets' solve; [(targets, uncertainty)] per attribute, on the device (device tail) or on the host."""
         tgt = self.finish_dynamic_targets()
-        targets = tgt[0][0]
-        if dv:
-            rb.update(targets=targets, uncertainty=tgt[0][1])
+        if self.device_tail:
+            st.rb.update(targets=tgt[0][0], uncertainty=tgt[0][1])
         else:
-            out.update(targets=targets, uncertainty=tgt[0][1], targets_by_attr={a["name"]: t for a, (t, _) in zip(per, tgt)})
-        # ---- R3: rollout with gradient (:1889-1933), all micro-batches at once with weights 1/n_j
-        w, N_backward = microbatch_weights(B, args.train_GPU_batch_size)
-        if share:
-            (enc_g, inputs, ctxs), images_g, ind_g, boxes_g, per_g = shared, images, ind, boxes, per
-        else:
-            self._mark("R3_fwd_rollout")
-            enc_g = self.encode_pair(self.te, tokens, record=rec_te, prefix=pv)
-            x_final, inputs, ctxs = self.rollout(self.unet, enc_g, noises, S, keep_inputs=True, record_prompt=True,
-                                                 keep_activations=self.keep_activations)
-            self._mark("R3_fwd_vae")
-            images_g = self.decode(x_final, record=True)
-            ind_g, boxes_g, per_g = self.classify_dev(self.classify_begin(images_g, record=True)) if dv else self.classify(images_g, record=True)
-        self._mark("R3_loss_and_image_grad")
-        loss_by_attr = {}
-        if dv:
+            st.out.update(targets=tgt[0][0], uncertainty=tgt[0][1], targets_by_attr={a["name"]: t for a, (t, _) in zip(per, tgt)})
+        return tgt
+
+    def _fair_loss(self, st, gen, tgt):
+        """loss_fair and its logit gradient ``dlog_full`` [B, classes] fp32 -- device tail: one attribute, on the device; host tail: summed over
+        the attributes (:1932; exp-3 :2146), on the host."""
+        if self.device_tail:
             name, c0, k = self.attrs[0]
-            ind_dev, w_dev = per_g[0]["ind_dev"], _h2d(w, dev)
-            lf, dl = FD.fair_loss_and_grad(per_g[0]["logits"], targets, ind_dev, w_dev)
-            dlog_full = torch.zeros((B, self.clf.num_classes), dtype=F32, device=dev)
+            lf, dl = FD.fair_loss_and_grad(gen["per"][0]["logits"], tgt[0][0], gen["per"][0]["ind_dev"], st.w_dev)
+            dlog_full = torch.zeros((st.B, self.clf.num_classes), dtype=F32, device=self.device)
             dlog_full[:, c0:c0 + k] = dl
-            rb["loss_fair"] = lf
-            out.update(images_grad=images_g, N_backward=N_backward)
+            st.rb["loss_fair"] = lf
+            st.out.update(images_grad=gen["images"], N_backward=st.N_backward)
         else:
-            dlog_full = torch.zeros((B, self.clf.num_classes), dtype=F32)
-            for (name, c0, k), a, (t_a, _) in zip(self.attrs, per_g, tgt):      # loss_ij = sum over attributes (:1932; exp-3 :2146)
-                lf, dl = fair_loss_and_grad(a["logits"], t_a, ind_g, w)
-                loss_by_attr[name] = lf
-                dlog_full[:, c0:c0 + k] = dl
-            loss_fair = loss_by_attr[self.attrs[0][0]]
-            out.update(loss_fair=loss_fair, loss_fair_by_attr=loss_by_attr, images_grad=images_g, N_backward=N_backward)
-        sel = ind_g.nonzero().view(-1)
+            loss_by_attr = {}
+            dlog_full = torch.zeros((st.B, self.clf.num_classes), dtype=F32)
+            for (name, c0, k), a, (t_a, _) in zip(self.attrs, gen["per"], tgt):
+                loss_by_attr[name], dlog_full[:, c0:c0 + k] = fair_loss_and_grad(a["logits"], t_a, gen["ind"], st.w)
+            st.out.update(loss_fair=loss_by_attr[self.attrs[0][0]], loss_fair_by_attr=loss_by_attr, images_grad=gen["images"], N_backward=st.N_backward)
+        return dlog_full
+
+    def _image_term(self, st, gen, ori, tgt):
+        """Image-semantics term (:1904-1910, :1931-1932): w_i = (1/n_j) * weight_loss_img * dynamic_weight_i.  Returns its image gradient [B,3,H,W]."""
+        args, dev, dv, out = self.args, self.device, self.device_tail, st.out
+        images_g, targets, preds_o = gen["images"], tgt[0][0], ori["per"][0]["preds"]
         Himg, Wimg = images_g.shape[2], images_g.shape[3]
-        d_img = None
-        deferred = []          # host read-backs of reported values: executed once the whole backward has been enqueued
-        if self.use_img_loss:
-            # image-semantics term (:1904-1910, :1931-1932): w_i = (1/n_j) * weight_loss_img * dynamic_weight_i
-            if share and pre_g is not None:
-                fullbox, e_c, e_d = pre_g            # enqueued ahead of the tail's first read-back (see classify_targets above)
-            else:
-                small, fullbox = self.resize_small(images_g)
-                e_c, e_d = self.image_features(small, record=True)
-            self._fine("L_a_clip_dino_fwd_enqueued")
-            tl, pl = [t for t, _ in tgt], [a["preds"] for a in per_o]
-            if dv:
-                dyn = FD.dynamic_weights(ind_dev, targets, per_o[0]["preds"], self.factors1[0])
-                wi = w_dev * args.weight_loss_img * dyn
-            else:
-                if len(tl) == 1:
-                    dyn = gen_dynamic_weights(ind_g, targets, per_o[0]["preds"], factor=self.factors1[0])
-                else:
-                    dyn = gen_dynamic_weights_multi(ind_g, tl, pl, self.factors1)
-                wi = _h2d(w * args.weight_loss_img * dyn, dev)
-            loss_clip, de_c = feature_loss_and_grad(e_c, clip_ori, wi)
-            loss_dino, de_d = feature_loss_and_grad(e_d, dino_ori, wi)
-            am = torch.stack([de_c.abs().max(), de_d.abs().max()]).float()
-            if _HOST_SCALES:
-                am = am.cpu()        # ONE read-back for both scales
-                self._fine("L_b_after_amax_readback")
-                dsmall = self.clip.backward(de_c, _pow2_scale(float(am[0]), 1.0))
-                self.dino.backward(de_d, _pow2_scale(float(am[1]), 1.0), out=dsmall)
-            else:
-                # power-of-two scales chosen on the device: the scaled gradient enters with gscale = 1 and the result is un-scaled by the
-                # exact inverse (a power-of-two multiply commutes with every rounding: same bits as the host-scale path)
-                sc = _pow2_scale_dev(am, 1.0)
-                dsmall = self.clip.backward(de_c * sc[0], 1.0).mul_(1.0 / sc[0])
-                dsmall.addcmul_(self.dino.backward(de_d * sc[1], 1.0), 1.0 / sc[1])
-            d_img = ops.crop_resize_bwd(dsmall, fullbox, B, Himg, Wimg, args.img_size_small)
-            # apply_grad_hook_face (:1904, :1584-1617) acts on this path only: the classifier saw the un-hooked images
-            if dv:       # the rectangle is a function of the two boxes (host); the factor of targets / original predictions (device)
-                zt = torch.zeros(B, dtype=torch.long)
-                rects, _ = face_grad_factors(boxes_g, boxes_o, zt, zt, 1.0, Himg, Wimg)
-                has_box = _h2d(~(boxes_g == -1).all(dim=1), dev)
-                ops.rect_scale(d_img, _h2d(rects, dev), FD.hook_factors(has_box, targets, per_o[0]["preds"], self.factors2[0]))
-                rb.update(loss_CLIP=loss_clip.float(), loss_DINO=loss_dino.float(), dynamic_weights=dyn)
-            else:
-                if len(tl) == 1:
-                    rects, facs = face_grad_factors(boxes_g, boxes_o, targets, per_o[0]["preds"], self.factors2[0], Himg, Wimg)
-                else:
-                    rects, facs = face_grad_factors_multi(boxes_g, boxes_o, tl, pl, self.factors2, Himg, Wimg)
-                ops.rect_scale(d_img, _h2d(rects, dev), _h2d(facs, dev))
-                # (the per-image regulariser values are only reported: they are read back at the end of the step, not here)
-                deferred.append(lambda lc=loss_clip, ld=loss_dino: out.update(
-                    loss_CLIP=lc.float().cpu(), loss_DINO=ld.float().cpu(), dynamic_weights=dyn,
-                    loss=sum(loss_by_attr.values()) + args.weight_loss_img * dyn * (lc.float().cpu() + ld.float().cpu())))
-            self._fine("L_c_clip_dino_bwd_enqueued")
-        if self.use_face_loss:
-            # face-realism term (:1917-1932): target = the original image's own face features when the target class equals the
-            # original prediction with confidence >= face_gender_confidence_level, else the nearest database face
-            from .sfnet import face_features, face_features_backward
-            # exp-1 searches only for images with a target (:1926); the multi-attribute scripts search for every face (exp-3 :2135)
-            if dv:
-                # which faces carry a target is only known on the device: every face goes through the face network and the ones without a
-                # target get weight 0 (same loss and gradient: their term is multiplied out; the reference skips them, :1926)
-                from_ori = ind_dev & (targets != -1) & (targets == per_o[0]["preds"]) & (per_o[0]["probs"].max(dim=-1).values >= self.face_conf)
-                has_d = ind_dev & (targets != -1)
-                has = ind_g
-                loss_face = torch.full((B,), -1.0, dtype=F32, device=dev)
-            else:
-                from_ori = ind_g.clone()
-                for (t_a, _), a in zip(tgt, per_o):
-                    from_ori &= (t_a != -1) & (t_a == a["preds"]) & (a["probs"].max(dim=-1).values >= self.face_conf)
-                has = (ind_g & (targets != -1)) if len(tgt) == 1 else ind_g.clone()
-                loss_face = torch.full((B,), -1.0)
-            rows = has.nonzero().view(-1)
-            if len(rows):
-                chips_f, idx_f, A_f = self.aligned_faces(images_g, has)
-                self._fine("L_c1_aligned_faces")
-                feats, fctx = face_features(self.face_net, chips_f, record=True)
-                self._fine("L_c2_sfnet_fwd_enqueued")
-                fn = F.normalize(feats, dim=-1)
-                tgt = self.nearest_face_feats(fn)
-                rows_d = _h2d(rows, dev)
-                use_ori = from_ori[rows_d] if dv else _h2d(from_ori[rows], dev)
-                tgt = torch.where(use_ori[:, None], face_ori[rows_d], tgt)
-                wf = (w_dev[rows_d] * args.weight_loss_face * has_d[rows_d]) if dv else _h2d(w[rows] * args.weight_loss_face, dev)
-                lf_rows, df = feature_loss_and_grad(feats, tgt, wf)
-                self._fine("L_c3_nearest_and_loss_enqueued")
-                if dv:
-                    loss_face[rows_d] = torch.where(has_d[rows_d], lf_rows.float(), torch.full_like(lf_rows, -1.0, dtype=F32))
-                else:
-                    deferred.append(lambda lf_rows=lf_rows, rows=rows: loss_face.__setitem__(rows, lf_rows.float().cpu()))
-                if _HOST_SCALES:
-                    dfmax = float(df.abs().max())
-                    self._fine("L_c4_df_amax_readback")
-                    dch = face_features_backward(self.face_net, fctx, df, _pow2_scale(dfmax, 1.0))
-                else:
-                    sf = _pow2_scale_dev(df.abs().max(), 1.0)
-                    dch = face_features_backward(self.face_net, fctx, df * sf, 1.0).mul_(1.0 / sf)
-                self._fine("L_c5_sfnet_bwd_enqueued")
-                if d_img is None:
-                    d_img = torch.zeros((B, 3, Himg, Wimg), dtype=F32, device=dev)
-                ops.warp_affine_bwd(dch.contiguous(), idx_f, A_f, d_img, args.size_aligned_face)   # un-hooked images (:1901)
-            if dv:
-                rb["loss_face"] = loss_face
-            else:
-                deferred.append(lambda: out.update(loss_face=loss_face, loss=out.get("loss", sum(loss_by_attr.values())) + args.weight_loss_face * loss_face))
-            self._fine("L_d_face_branch_done")
-        # (device_tail: whether any logit gradient is non-zero is not known to the host -- the classifier backward runs whenever there is a face)
-        any_dlog = bool(len(sel)) and (dv or float(dlog_full.abs().sum()) > 0)
-        if any_dlog or d_img is not None:
-            if any_dlog:
-                dlog = dlog_full[_h2d(sel, dev)] if dv else _h2d(dlog_full[sel], dev)
-                dchips = self.clf.backward(dlog.contiguous(), self.clf_gscale)
-                full = dchips
-                if len(sel) != B:
-                    full = torch.zeros((B,) + tuple(dchips.shape[1:]), dtype=F32, device=dev)
-                    full[_h2d(sel, dev)] = dchips
-                bx = boxes_g.clone()
-                bx[~ind_g] = 0
-                d_fair = ops.crop_resize_bwd(full.contiguous(), _h2d(bx, dev), B, Himg, Wimg, args.size_face)
-                d_img = d_fair if d_img is None else d_img.add_(d_fair)
-            else:
-                self.clf._ctx = None
-            self._mark("R3_bwd_vae")
-            coefs = self.sch.grad_coefs() * self.sch.chain_coefs()   # hook (:1128) x scheduler recurrence (:1131)
-            gs = args.guidance_scale
-            if _HOST_SCALES:
-                vscale = _pow2_scale(float(d_img.abs().max()), 64.0)
-                dz = self.vae.backward_images(d_img, vscale)
-                g = dz * (1.0 / self.vae.config.scaling_factor)          # dL/dx_final  [B,4,h,w] fp32
-                gscale = _pow2_scale(float(g.abs().max()) * float(abs(coefs).max()) * max(abs(gs), abs(1 - gs)), 64.0)
-                step_scale, inv_gscale = [float(c * gscale) for c in coefs], None
-            else:
-                vs = _pow2_scale_dev(d_img.abs().max(), 64.0)
-                dz = self.vae.backward_images(d_img * vs, 1.0)
-                g = dz * ((1.0 / self.vae.config.scaling_factor) / vs)   # dL/dx_final  [B,4,h,w] fp32
-                # the U-Net backward's scale stays on the device too: the timesteps' upstream gradients are multiplied by (c_i * gscale) as device
-                # scalars, the kernels run with gscale = 1 and the LoRA gradients are un-scaled ONCE, after the per-stream buffers have been summed
-                gscale_dev = _pow2_scale_dev(g.abs().max() * (float(abs(coefs).max()) * max(abs(gs), abs(1 - gs))), 64.0)
-                step_scale = _h2d(torch.as_tensor(coefs, dtype=F32), dev) * gscale_dev
-                inv_gscale, gscale = 1.0 / gscale_dev, 1.0
-            out.update(g=g, coefs=coefs, gscale=gscale)
-            self._mark("R3_bwd_unet")
-            if train_unet or train_te or train_prefix:
-                # The S per-timestep backwards are independent (the U-Net input is detached at every step, :1115): they are dealt round-robin
-                # to ``bwd_streams`` HIP streams, each side stream accumulating its LoRA gradients into its own buffer, so that the many
-                # launches which cannot fill the chip alone overlap with a neighbouring timestep's.  Shared cross-attention dK/dV: fp32 atomics.
-                cur = torch.cuda.current_stream()
-                self.unet.prepare_backward()         # lazily built weight copies exist before any side stream can read them
-                if not _ATOMIC_DKDV:
-                    self.unet.prepare_backward_slots(S)   # per-timestep dK / dV pairs of the shared cross-attention K / V: no atomics, fixed-order sum
-                nst = max(1, min(self.bwd_streams, S)) if self.concurrent_bwd else 1
-                sides = [self._side_stream(k) for k in range(1, nst)]
-                virtual = self.bwd_virtual
-                graveyard = [] if self.bwd_keep_alive else None
-                # upstream gradient of the CFG pair eps = eps_u + gs (eps_c - eps_u): [(1 - gs) g ; gs g], built once; a timestep scales it.
-                # Built on the launch stream BEFORE the side streams take their dependency on it: enqueued after ``wait_stream`` (as it was for
-                # most of round 3) the side streams' first timesteps could read it while its ``cat`` was still running -- a race that showed
-                # as a 4e-4 schedule-to-schedule gradient difference (once as NaN) whenever kernel timing shifted.
-                gpair = torch.cat([g * (1.0 - gs), g * gs])
-                for k, side in enumerate(sides, 1):
-                    for bank in self.banks:
-                        bank.grad_alt(k).zero_()
-                    side.wait_stream(cur)
-                for i in range(S):
-                    k = i % nst
-                    on_side = k > 0
-                    side = sides[k - 1] if on_side else None
-                    with (torch.cuda.stream(side) if (on_side and not virtual) else contextlib.nullcontext()):
-                        if i in ctxs:
-                            self.unet._ctx = ctxs.pop(i)        # activations kept from the forward rollout
-                            if graveyard is not None:
-                                graveyard.append(_all_tensors(self.unet._ctx))
-                            if on_side and not virtual:
-                                _record_stream(self.unet._ctx, side)
-                        else:                                   # gradient-checkpointed recompute of this timestep
-                            x = ops.to_f16(inputs[i])
-                            self.unet.forward_step(x if _CFG_PAIR else x.repeat(2, 1, 1, 1), i, record=True, pair=_CFG_PAIR)
-                        for bank in self.banks:
-                            bank.accum = bank.grad_alt(k) if on_side else bank.grad
-                        unet_mod.BWD_SLOT[0] = i
-                        self.unet.backward_step(gpair * step_scale[i], gscale)
-                unet_mod.BWD_SLOT[0] = None
-                for bank in self.banks:
-                    bank.accum = bank.grad
-                if self.debug_partials is not None:
-                    torch.cuda.synchronize()
-                    self.debug_partials.append([self.banks[0].grad.clone()] + [self.banks[0].grad_alt(k).clone() for k in range(1, nst)])
-                for k, side in enumerate(sides, 1):
-                    cur.wait_stream(side)
-                    for bank in self.banks:
-                        bank.grad.add_(bank.grad_alt(k))
-                graveyard = None
-                denc = self.unet.finish_prompt_backward(gscale, need_denc=rec_te)
-                if rec_te:
-                    L = enc_g.shape[1]
-                    dx0 = self.te.backward(denc.view(2, L, -1), gscale)
-                    if train_prefix:     # the prefix vectors sit at positions 1..n of the PROMPT row (row 1; row 0 is the uncond sequence)
-                        n = self.prefix.n
-                        self.prefix.bank.grad_view("token_embedding.weight")[1:].add_(dx0[1, 1:1 + n].float(), alpha=1.0 / gscale)
-                if inv_gscale is not None:      # device-side loss scale: every bank's gradient of this step carries it exactly once
-                    for bank in self.banks:
-                        bank.grad.mul_(inv_gscale)
+        small, fullbox = self.resize_small(images_g)
+        e_c, e_d = self.image_features(small, record=True)
+        self._fine("L_a_clip_dino_fwd_enqueued")
+        tl, pl = [t for t, _ in tgt], [a["preds"] for a in ori["per"]]
+        if dv:
+            dyn = FD.dynamic_weights(gen["per"][0]["ind_dev"], targets, preds_o, self.factors1[0])
+            wi = st.w_dev * args.weight_loss_img * dyn
         else:
-            self.vae._ctx = self.clf._ctx = None
-        ctxs.clear()
-        if self._r2_pre is not None and self.r2_prefetch_late > 0:
-            k2 = max(0, min(self.r2_prefetch_late, self._r2_pre["S"] - self._r2_pre["k"]))
-            with torch.cuda.stream(self._side_stream("r2")):
-                for _ in range(k2):
-                    next(self._r2_pre["gen"], None)
-            self._r2_pre["k"] += k2
-        for fn in deferred:
-            fn()
-        # ---- gradient sync, guard, update (:1998-2029)
-        self._mark("sync_update")
-        if dv:       # ONE read-back for everything the step reports, taken together with the finite flag inside sync_and_update
+            dyn = gen_dynamic_weights(gen["ind"], targets, preds_o, factor=self.factors1[0]) if len(tl) == 1 else \
+                gen_dynamic_weights_multi(gen["ind"], tl, pl, self.factors1)
+            wi = _h2d(st.w * args.weight_loss_img * dyn, dev)
+        loss_clip, de_c = feature_loss_and_grad(e_c, ori["clip"], wi)
+        loss_dino, de_d = feature_loss_and_grad(e_d, ori["dino"], wi)
+        sc = _pow2_scale_dev(torch.stack([de_c.abs().max(), de_d.abs().max()]).float(), 1.0)      # both scales in one chain of launches
+        dsmall, inv = _scaled_backward(self.clip.backward, de_c, sc[0])
+        dsmall.mul_(inv)
+        dd, inv = _scaled_backward(self.dino.backward, de_d, sc[1])
+        dsmall.addcmul_(dd, inv)
+        d_img = ops.crop_resize_bwd(dsmall, fullbox, st.B, Himg, Wimg, args.img_size_small)
+        # apply_grad_hook_face (:1904, :1584-1617) acts on this path only: the classifier saw the un-hooked images
+        if dv:       # the rectangle is a function of the two boxes (host); the factor of targets / original predictions (device)
+            zt = torch.zeros(st.B, dtype=torch.long)
+            rects, _ = face_grad_factors(gen["boxes"], ori["boxes"], zt, zt, 1.0, Himg, Wimg)
+            has_box = _h2d(~(gen["boxes"] == -1).all(dim=1), dev)
+            ops.rect_scale(d_img, _h2d(rects, dev), FD.hook_factors(has_box, targets, preds_o, self.factors2[0]))
+            st.rb.update(loss_CLIP=loss_clip.float(), loss_DINO=loss_dino.float(), dynamic_weights=dyn)
+        else:
+            rects, facs = face_grad_factors(gen["boxes"], ori["boxes"], targets, preds_o, self.factors2[0], Himg, Wimg) if len(tl) == 1 else \
+                face_grad_factors_multi(gen["boxes"], ori["boxes"], tl, pl, self.factors2, Himg, Wimg)
+            ops.rect_scale(d_img, _h2d(rects, dev), _h2d(facs, dev))
+            # (the per-image regulariser values are only reported: they are read back at the end of the step, not here)
+            st.deferred.append(lambda lc=loss_clip, ld=loss_dino: out.update(
+                loss_CLIP=lc.float().cpu(), loss_DINO=ld.float().cpu(), dynamic_weights=dyn,
+                loss=sum(out["loss_fair_by_attr"].values()) + args.weight_loss_img * dyn * (lc.float().cpu() + ld.float().cpu())))
+        self._fine("L_c_clip_dino_bwd_enqueued")
+        return d_img
+
+    def _face_term(self, st, gen, ori, tgt, d_img):
+        """Face-realism term (:1917-1932): target = the original image's own face features when the target class equals the original prediction
+        with confidence >= face_gender_confidence_level, else the nearest database face.  Adds its image gradient to ``d_img`` (None: a new one)."""
+        args, dev, dv, out, B = self.args, self.device, self.device_tail, st.out, st.B
+        images_g, ind_g, targets = gen["images"], gen["ind"], tgt[0][0]
+        # exp-1 searches only for images with a target (:1926); the multi-attribute scripts search for every face (exp-3 :2135)
+        if dv:
+            # which faces carry a target is only known on the device: every face goes through the face network and the ones without a
+            # target get weight 0 (same loss and gradient: their term is multiplied out; the reference skips them, :1926)
+            ind_dev, per_o = gen["per"][0]["ind_dev"], ori["per"][0]
+            from_ori = ind_dev & (targets != -1) & (targets == per_o["preds"]) & (per_o["probs"].max(dim=-1).values >= self.face_conf)
+            has_d = ind_dev & (targets != -1)
+            has = ind_g
+            loss_face = torch.full((B,), -1.0, dtype=F32, device=dev)
+        else:
+            from_ori = ind_g.clone()
+            for (t_a, _), a in zip(tgt, ori["per"]):
+                from_ori &= (t_a != -1) & (t_a == a["preds"]) & (a["probs"].max(dim=-1).values >= self.face_conf)
+            has = (ind_g & (targets != -1)) if len(tgt) == 1 else ind_g.clone()
+            loss_face = torch.full((B,), -1.0)
+        rows = has.nonzero().view(-1)
+        if len(rows):
+            chips_f, idx_f, A_f = self.aligned_faces(images_g, has)
+            self._fine("L_c1_aligned_faces")
+            feats, fctx = face_features(self.face_net, chips_f, record=True)
+            self._fine("L_c2_sfnet_fwd_enqueued")
+            near = self.nearest_face_feats(F.normalize(feats, dim=-1))
+            rows_d = _h2d(rows, dev)
+            use_ori = from_ori[rows_d] if dv else _h2d(from_ori[rows], dev)
+            near = torch.where(use_ori[:, None], ori["face"][rows_d], near)
+            wf = (st.w_dev[rows_d] * args.weight_loss_face * has_d[rows_d]) if dv else _h2d(st.w[rows] * args.weight_loss_face, dev)
+            lf_rows, df = feature_loss_and_grad(feats, near, wf)
+            self._fine("L_c3_nearest_and_loss_enqueued")
+            if dv:
+                loss_face[rows_d] = torch.where(has_d[rows_d], lf_rows.float(), torch.full_like(lf_rows, -1.0, dtype=F32))
+            else:
+                st.deferred.append(lambda: loss_face.__setitem__(rows, lf_rows.float().cpu()))
+            dch, inv = _scaled_backward(partial(face_features_backward, self.face_net, fctx), df, _pow2_scale_dev(df.abs().max(), 1.0))
+            dch.mul_(inv)
+            self._fine("L_c5_sfnet_bwd_enqueued")
+            if d_img is None:
+                d_img = torch.zeros((B, 3, images_g.shape[2], images_g.shape[3]), dtype=F32, device=dev)
+            ops.warp_affine_bwd(dch.contiguous(), idx_f, A_f, d_img, args.size_aligned_face)   # un-hooked images (:1901)
+        if dv:
+            st.rb["loss_face"] = loss_face
+        else:
+            st.deferred.append(lambda: out.update(loss_face=loss_face, loss=out.get("loss", sum(out["loss_fair_by_attr"].values())) + args.weight_loss_face * loss_face))
+        self._fine("L_d_face_branch_done")
+        return d_img
+
+    def _classifier_backward(self, st, gen, dlog_full, d_img):
+        """dlog_full through the classifier and the face crops back to the image, added to the regularisers' ``d_img``.  Returns dL/d(images), or None
+        when no term has a gradient.  The classifier's recorded forward is consumed or dropped here."""
+        dev, dv, B = self.device, self.device_tail, st.B
+        sel = gen["ind"].nonzero().view(-1)
+        # (device_tail: whether any logit gradient is non-zero is not known to the host -- the classifier backward runs whenever there is a face)
+        if not (bool(len(sel)) and (dv or float(dlog_full.abs().sum()) > 0)):
+            self.clf._ctx = None
+            return d_img
+        dlog = dlog_full[_h2d(sel, dev)] if dv else _h2d(dlog_full[sel], dev)
+        dchips = self.clf.backward(dlog.contiguous(), self.clf_gscale)
+        full = dchips
+        if len(sel) != B:
+            full = torch.zeros((B,) + tuple(dchips.shape[1:]), dtype=F32, device=dev)
+            full[_h2d(sel, dev)] = dchips
+        bx = gen["boxes"].clone()
+        bx[~gen["ind"]] = 0
+        d_fair = ops.crop_resize_bwd(full.contiguous(), _h2d(bx, dev), B, gen["images"].shape[2], gen["images"].shape[3], self.args.size_face)
+        return d_fair if d_img is None else d_img.add_(d_fair)
+
+    def _vae_backward(self, st, d_img):
+        """dL/d(images) -> g = dL/dx_final [B,4,h,w] fp32, and the U-Net backward's scales: ``step_scale`` [S] (device) = hook (:1128) x scheduler
+        recurrence (:1131) x the step's common power-of-two loss scale, whose inverse ``inv_gscale`` un-scales the LoRA gradients at the very end."""
+        coefs, gs = self.sch.grad_coefs() * self.sch.chain_coefs(), self.args.guidance_scale
+        dz, k = _scaled_backward(self.vae.backward_images, d_img, _pow2_scale_dev(d_img.abs().max(), 64.0), unscale=1.0 / self.vae.config.scaling_factor)
+        g = dz * k
+        # the U-Net backward's scale stays on the device too: the timesteps' upstream gradients are multiplied by (c_i * gscale) as device
+        # scalars, the kernels run with gscale = 1 and the LoRA gradients are un-scaled ONCE, after the per-stream buffers have been summed
+        gscale_dev = _pow2_scale_dev(g.abs().max() * (float(abs(coefs).max()) * max(abs(gs), abs(1 - gs))), 64.0)
+        step_scale = _h2d(torch.as_tensor(coefs, dtype=F32), self.device) * gscale_dev
+        st.out.update(g=g, coefs=coefs, gscale=1.0)
+        return g, step_scale, 1.0 / gscale_dev
+
+    def _unet_backward(self, st, gen, g, step_scale, inv_gscale):
+        """The S per-timestep backwards are independent (the U-Net input is detached at every step, :1115): they are dealt round-robin to
+        ``bwd_streams`` HIP streams, each side stream accumulating its LoRA gradients into its own buffer, so that the many launches which cannot
+        fill the chip alone overlap with a neighbouring timestep's.  Then the prompt projections' and the text encoder's / prefix's backward."""
+        S, gs, cur, ctxs, virtual = st.S, self.args.guidance_scale, st.cur, gen["ctxs"], self.bwd_virtual
+        self.unet.prepare_backward()         # lazily built weight copies exist before any side stream can read them
+        self.unet.prepare_backward_slots(S)   # per-timestep dK / dV pairs of the shared cross-attention K / V: no atomics, fixed-order sum
+        nst = max(1, min(self.bwd_streams, S)) if self.concurrent_bwd else 1
+        sides = [self._side_stream(k) for k in range(1, nst)]
+        graveyard = [] if self.bwd_keep_alive else None
+        # upstream gradient of the CFG pair eps = eps_u + gs (eps_c - eps_u): [(1 - gs) g ; gs g], built once; a timestep scales it.
+        # Built on the launch stream BEFORE the side streams take their dependency on it: enqueued after ``wait_stream`` (as it was for
+        # most of round 3) the side streams' first timesteps could read it while its ``cat`` was still running -- a race that showed
+        # as a 4e-4 schedule-to-schedule gradient difference (once as NaN) whenever kernel timing shifted.
+        gpair = torch.cat([g * (1.0 - gs), g * gs])
+        for k, side in enumerate(sides, 1):
+            for bank in self.banks:
+                bank.grad_alt(k).zero_()
+            side.wait_stream(cur)
+        for i in range(S):
+            k = i % nst
+            on_side = k > 0
+            side = sides[k - 1] if on_side else None
+            with (torch.cuda.stream(side) if (on_side and not virtual) else contextlib.nullcontext()):
+                if i in ctxs:
+                    self.unet._ctx = ctxs.pop(i)        # activations kept from the forward rollout
+                    if graveyard is not None:
+                        graveyard.append(_all_tensors(self.unet._ctx))
+                    if on_side and not virtual:
+                        _record_stream(self.unet._ctx, side)
+                else:                                   # gradient-checkpointed recompute of this timestep
+                    self.unet.forward_step(ops.to_f16(gen["inputs"][i]), i, record=True, pair=True)
+                for bank in self.banks:
+                    bank.accum = bank.grad_alt(k) if on_side else bank.grad
+                unet_mod.BWD_SLOT[0] = i
+                self.unet.backward_step(gpair * step_scale[i], 1.0)
+        unet_mod.BWD_SLOT[0] = None
+        for bank in self.banks:
+            bank.accum = bank.grad
+        if self.debug_partials is not None:
+            torch.cuda.synchronize()
+            self.debug_partials.append([self.banks[0].grad.clone()] + [self.banks[0].grad_alt(k).clone() for k in range(1, nst)])
+        for k, side in enumerate(sides, 1):
+            cur.wait_stream(side)
+            for bank in self.banks:
+                bank.grad.add_(bank.grad_alt(k))
+        graveyard = None
+        denc = self.unet.finish_prompt_backward(1.0, need_denc=st.rec_te)
+        if st.rec_te:
+            dx0 = self.te.backward(denc.view(2, gen["enc"].shape[1], -1), 1.0)
+            if st.train_prefix:     # the prefix vectors sit at positions 1..n of the PROMPT row (row 1; row 0 is the uncond sequence)
+                self.prefix.bank.grad_view("token_embedding.weight")[1:].add_(dx0[1, 1:1 + self.prefix.n].float())
+        for bank in self.banks:      # device-side loss scale: every bank's gradient of this step carries it exactly once
+            bank.grad.mul_(inv_gscale)
+
+    def _sync_and_report(self, st):
+        """Gradient sync, guard and update; what the step reports about itself.  Device tail: everything in ``st.rb`` comes back in ONE read-back,
+        taken together with the finite flag inside ``sync_and_update``, and the reported loss is assembled from it on the host."""
+        args, out, rb, dv = self.args, st.out, st.rb, self.device_tail
+        if dv:
             keys = sorted(rb)
             self._pending_readback = torch.cat([rb[k].reshape(-1).to(F32) for k in keys]) if keys else None
-        out["grad_is_finite"] = self.sync_and_update(N_backward)
+        out["grad_is_finite"] = self.sync_and_update(st.N_backward)
         if dv:
             host = self._readback_host if self._pending_readback is None else self._pending_readback.cpu()    # (a replaced sync_and_update: read here)
             self._pending_readback = None
@@ -1173,12 +1156,10 @@ class FairnessTrainer:
                 out["loss"] = out["loss"] + args.weight_loss_img * out["dynamic_weights"] * (out["loss_CLIP"] + out["loss_DINO"])
             if "loss_face" in out:
                 out["loss"] = out["loss"] + args.weight_loss_face * out["loss_face"]
-        if mon is not None:
+        if self._mon is not None:
             # behind the step's own read-back (``sync_and_update``), which has drained the stream the copies were queued on: no further wait
-            mon.pop("event").synchronize()
-            self.last_monitor, self._mon = mon, None
-        self._mark("end")
-        return out
+            self._mon.pop("event").synchronize()
+            self.last_monitor, self._mon = self._mon, None
 
     def sync_and_update(self, N_backward, apply=True):
         args = self.args
