@@ -16,7 +16,8 @@
 //       the B operand of O^T[dv][query] = V^T[dv][key] . P^T[key][query] (A = rows of the transposed V the caller prepared once per rollout; the
 //       contraction's k-slots are key tiles (2j, 2j + 1) x 4 keys, the same order on both operands).  o overwrites the q columns of its head;
 //   P3  h2 = o . Wo^T as P1; fp16(acc + bias) is staged in the tile, then one wave per row adds the residual h1 (fp16(staged + h1): the
-//       rounding sequence of fd_gemm's LDS-staged epilogue, bit-identical h2 for identical o), stores h2, and LayerNorm3 of the row (as P0) -> n3.
+//       rounding sequence of the fp16 library's LDS-staged fd_gemm epilogue, bit-identical h2 for identical o there; the bf16 library's fd_gemm
+//       rounds once, after the residual), stores h2, and LayerNorm3 of the row (as P0) -> n3.
 //
 // Algorithmic HBM traffic per row: read h1 twice (the second read is an L2 hit), write h2 and n3: 4 C * 2 B against 14 C * 2 B unfused.
 // Template arguments: LORA -- the LoRA slabs of attn2.to_q / to_out ride in the kernel: t = tile . down^T (N = the padded rank, one 16-row MFMA tile per wave, rounded to

@@ -124,6 +124,13 @@ __device__ __forceinline__ void gemm_epilogue(const fd_gemm_desc& p, f32x4 (&acc
 }
 
 
+// residual of C[m][n..n+3] as fp32, zeros outside the matrix (ldr % 8 == 0 and N % 8 == 0 by FD_GEMM_LDS_EPILOGUE_OK: one aligned 8-byte load)
+__device__ __forceinline__ f32x4 staged_residual(const f16* R, const fd_gemm_desc& p, int m, int n) {
+    if (m >= p.M || n >= p.N) return (f32x4){0.f, 0.f, 0.f, 0.f};
+    const f16x4 rv = *(const f16x4*)(R + (int64_t)m * p.ldr + n);
+    return (f32x4){(float)rv[0], (float)rv[1], (float)rv[2], (float)rv[3]};
+}
+
 // ---- LDS-staged epilogue (fp16 output): the accumulator layout gives each lane 4 consecutive N (8 bytes), i.e. 32-byte
 // row segments per store instruction; short-K GEMMs are bound by exactly that store path.  Here each wave parks its
 // WTM x WTN tile in LDS (bias / row-bias / activation already applied) and re-reads it as 16 bytes per lane so that a
@@ -136,7 +143,16 @@ __device__ __forceinline__ void gemm_epilogue_lds(const fd_gemm_desc& p, f32x4 (
     static_assert(TM % TMC == 0, "chunking");
     const int l15 = lane & 15, lg = lane >> 4;
     const f16* RB = (const f16*)p.rowbias;
+#ifdef FD_BF16
+    // bf16 has 8 significand bits: a value rounded for the staging and rounded again after the residual is added is off by up to half an ulp of the
+    // LARGER of the two, many ulps of a sum that cancels.  The residual therefore joins the fp32 value before the staging (8-byte loads in the
+    // accumulator layout, as gemm_epilogue does) and C is rounded once: bf16(act(...) + residual).  The fp16 library keeps the add on the way out.
+    const f16* const R = nullptr;
+    const f16* const RS = p.residual ? (const f16*)p.residual + zR : nullptr;
+#else
     const f16* R = p.residual ? (const f16*)p.residual + zR : nullptr;
+    const f16* const RS = nullptr;
+#endif
     constexpr int CPR = WTN / 8;                 // 16-byte chunks per row
     constexpr int RPI = 64 / CPR;                // rows per store instruction
     const int cr = lane / CPR, cc = (lane % CPR) * 8;
@@ -167,7 +183,8 @@ __device__ __forceinline__ void gemm_epilogue_lds(const fd_gemm_desc& p, f32x4 (
                 if (p.bias && n < p.N) bv = *(const f32x4*)(p.bias + n);
 #pragma unroll
                 for (int ii = 0; ii < TMC; ++ii) {
-                    const f32x4 v = acc[c0 + ii][j] + bv;
+                    f32x4 v = acc[c0 + ii][j] + bv;
+                    if (RS) v += staged_residual(RS, p, mbase + (c0 + ii) * 16 + l15, n);
                     *(f16x4*)(wave_lds + (ii * 16 + l15) * LDW + j * 16 + lg * 4) = (f16x4){(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
                 }
             }
@@ -180,7 +197,8 @@ __device__ __forceinline__ void gemm_epilogue_lds(const fd_gemm_desc& p, f32x4 (
                 const float cs = n < p.colscale_cols ? p.colscale : 1.f;
 #pragma unroll
                 for (int ii = 0; ii < TMC; ++ii) {
-                    const f32x4 v = acc[c0 + ii][j] * cs + bv;
+                    f32x4 v = acc[c0 + ii][j] * cs + bv;
+                    if (RS) v += staged_residual(RS, p, mbase + (c0 + ii) * 16 + l15, n);
                     *(f16x4*)(wave_lds + (ii * 16 + l15) * LDW + j * 16 + lg * 4) = (f16x4){(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
                 }
             }
@@ -198,12 +216,14 @@ __device__ __forceinline__ void gemm_epilogue_lds(const fd_gemm_desc& p, f32x4 (
                     f16x4 rbv = {0, 0, 0, 0};
                     if (RB && m < p.M && n < p.N) rbv = *(const f16x4*)(RB + (int64_t)(m / p.rows_per_batch) * p.ld_rowbias + n);
                     f16x4 o;
+                    f32x4 rs = {0.f, 0.f, 0.f, 0.f};
+                    if (RS) rs = staged_residual(RS, p, m, n);
                     if (p.act == FD_ACT_NONE) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) o[r] = (f16)(acc[i][j][r] * al + bv[r] + (float)rbv[r]);
+                        for (int r = 0; r < 4; ++r) o[r] = (f16)(acc[i][j][r] * al + bv[r] + (float)rbv[r] + rs[r]);
                     } else {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) o[r] = (f16)apply_act(acc[i][j][r] * al + bv[r] + (float)rbv[r], p.act);
+                        for (int r = 0; r < 4; ++r) o[r] = (f16)(apply_act(acc[i][j][r] * al + bv[r] + (float)rbv[r], p.act) + rs[r]);
                     }
                     if (FD_DBG_IS(p, 5)) o = (f16x4){(f16)acc[i][j][0], (f16)acc[i][j][1], (f16)acc[i][j][2], (f16)acc[i][j][3]};   // FD_GEMM_DBG=5
                     *(f16x4*)(wave_lds + (ii * 16 + l15) * LDW + j * 16 + lg * 4) = o;

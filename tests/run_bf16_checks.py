@@ -2,7 +2,9 @@
 at import (FD_DTYPE=bf16 selects libfairdiff_hip_bf16.so); tests/test_bf16_gpu.py launches it.
 
 Bands (bf16 has 8 significand bits against fp16's 11, i.e. 8x the rounding step; the reference itself never ran bf16):
-  kernels vs fp32 torch           2e-2 of max|ref|   (fp16 library: 2e-3 .. 5e-3)
+  kernels                         moved: the seven kernel checks that lived here (two GEMMs, a 3x3 convolution, GroupNorm, LayerNorm, attention forward and
+                                  backward at d=40) are in tests/run_bf16_kernel_checks.py at the same shapes, still held to the bands they had here
+                                  (1e-2 .. 3e-2 of max|ref|) beside that script's sharper gates; tests/test_kernels_bf16_gpu.py runs them
   tiny U-Net eps vs fp32 oracle   8e-2               (fp16: 2e-2);  LoRA gradients per family 2e-1 (fp16: 5e-2), cosine > 0.995
   SD-v1.5-size U-Net eps          4e-2 (relative RMS 2e-2)
   full tiny training step         images 1e-1, exact targets, loss_fair 5e-2, end-to-end gradient cosine > 0.8 (measured 0.87; ReLU / clamp mask flips)
@@ -42,40 +44,6 @@ def check(name, a, b, tol):
 
 def rnd(*shape, seed, scale=1.0):
     return (torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale).to(dev).to(BF)
-
-
-def kernels():
-    a, b = rnd(4096, 1280, seed=1), rnd(320, 1280, seed=2)
-    check("gemm 4096x320x1280", ops.gemm(a, b), a.float() @ b.float().t(), 1e-2)
-    a, b = rnd(65536, 320, seed=3), rnd(320, 320, seed=4)
-    bias = torch.randn(320, generator=torch.Generator().manual_seed(5)).to(dev)
-    res = rnd(65536, 320, seed=6)
-    check("gemm 65536x320x320 + bias + residual (256x320 tile)", ops.gemm(a, b, bias=bias, residual=res), a.float() @ b.float().t() + bias + res.float(), 1e-2)
-    x = rnd(2 * 32 * 32, 320, seed=7)
-    w = rnd(320, 9 * 320, seed=8, scale=0.02)
-    ref = F.conv2d(x.float().reshape(2, 32, 32, 320).permute(0, 3, 1, 2), w.float().reshape(320, 3, 3, 320).permute(0, 3, 1, 2), padding=1)
-    y, _, _ = ops.conv3x3(x, w, 2, 32, 32)
-    check("conv3x3 320->320 @32^2", y.reshape(2, 32, 32, 320).permute(0, 3, 1, 2), ref, 1e-2)
-    g, st = ops.groupnorm(x, None, 2, 1024, 32, 1e-5, torch.ones(320, device=dev), torch.zeros(320, device=dev), True)
-    check("groupnorm+silu", g.reshape(2, 1024, 320), F.silu(F.group_norm(x.float().reshape(2, 1024, 320).permute(0, 2, 1), 32, eps=1e-5)).permute(0, 2, 1), 2e-2)
-    n = ops.layernorm(x, torch.ones(320, device=dev), torch.zeros(320, device=dev))
-    check("layernorm", n, F.layer_norm(x.float(), (320,)), 2e-2)
-    B, H, T, d = 2, 8, 1024, 40
-    C = H * d
-    q, k, v = rnd(B, T, C, seed=11), rnd(B, T, C, seed=12), rnd(B, T, C, seed=13)
-    qr, kr, vr = (t.float().requires_grad_(True) for t in (q, k, v))
-    def sp(t):
-        return t.reshape(B, T, H, d).permute(0, 2, 1, 3)
-    s = sp(qr) @ sp(kr).transpose(-1, -2) * d ** -0.5
-    oref = (torch.softmax(s, -1) @ sp(vr)).permute(0, 2, 1, 3).reshape(B, T, C)
-    o, lse = ops.attn_fwd(q.reshape(B * T, C), k.reshape(B * T, C), v.reshape(B * T, C), B, H, T, T, d, 1, need_lse=True)
-    check("attention fwd d=40", o.reshape(B, T, C), oref, 2e-2)
-    do = rnd(B, T, C, seed=14)
-    oref.backward(do.float())
-    dq, dk, dv = ops.attn_bwd(q.reshape(B * T, C), k.reshape(B * T, C), v.reshape(B * T, C), o, do.reshape(B * T, C), lse, B, H, T, T, d, 1)
-    check("attention dq", dq.reshape(B, T, C), qr.grad, 3e-2)
-    check("attention dk", dk.reshape(B, T, C), kr.grad, 3e-2)
-    check("attention dv", dv.reshape(B, T, C), vr.grad, 3e-2)
 
 
 def tiny_unet_and_step():
@@ -232,9 +200,8 @@ def sd15_unet():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["kernels", "tiny", "sd15"]
-    if "kernels" in which:
-        kernels()
+    which = sys.argv[1:] or ["tiny", "sd15"]
+    assert all(w in ("tiny", "sd15", "exp3") for w in which), which
     if "tiny" in which:
         tiny_unet_and_step()
     if "sd15" in which:

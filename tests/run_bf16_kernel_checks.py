@@ -1,0 +1,1572 @@
+"""Kernel-by-kernel checks of the bf16 library (libfairdiff_hip_bf16.so, FD_DTYPE=bf16) against fp64 references -- run as a SCRIPT in its own
+process, because a process's working dtype is fixed at import; tests/test_kernels_bf16_gpu.py starts one child per group:
+
+    FD_DTYPE=bf16 python tests/run_bf16_kernel_checks.py gemm conv attention norm_elementwise bitexact small_classifier_eval
+
+RESIDUAL FINDING (fixed in gemm_device.h).  fd_gemm launches with a 16-bit output and a residual that go through the LDS-staged epilogue (gemm_epilogue_lds:
+every big-tile, ping-pong and halo kernel, and gemm_glds where N % 8 == 0) parked act(acc + bias) in LDS ROUNDED TO THE WORKING DTYPE and added the residual
+on the way out with a second rounding.  Gate B assumes one rounding and failed there: measured on the MI355X B1 max ratio 2.2 .. 85 (up to 5.06 M elements
+over at 204400x128x320), B2 row 2.0 .. 17.6 / col 1.9 .. 4.4 against the margin 1.25, while the same launches without the residual passed (B1 <= 1,
+B2 1.000), as did split-K and the skinny kernel.  In fp16 the second rounding stays inside the 2e-3 band; in bf16 it is up to one more half ulp of the
+pre-residual value, many ulp of a result that cancelled.  The bf16 library now adds the residual to the fp32 value before the staging and rounds once;
+the fp16 library's epilogue is unchanged.  Every residual launch below is also run without its residual, so either epilogue form stays covered.
+
+Inputs are bf16-representable (drawn in fp32, rounded to bf16, the rounded values used on both sides); references are plain fp64 PyTorch statements
+evaluated on the GPU.  Every check prints its figures; a group collects its failures, prints them and exits non-zero, or prints
+``BF16 KERNEL CHECKS PASSED <group>``.  The band helpers below are pure torch (no GPU, no library): tests/test_bf16_bands_cpu.py imports them.
+The seven checks the former ``kernels()`` of run_bf16_checks.py made are here at their shapes, with its band kept as an extra coarse gate (``legacy=``)."""
+import ctypes
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+BF = torch.bfloat16
+GRID = 4096 * 256          # threads of a full grid-stride launch (elementwise.hip grid_for)
+
+# ============================================================================= bands
+B2_MARGIN = 1.25
+
+
+def ulp_bf16(x):
+    """Spacing of bf16 numbers at magnitude |x| (fp64 tensor): 2^(floor(log2|x|) - 7); below the smallest normal the subnormal spacing 2^-133."""
+    a = x.abs().double().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 7)
+
+
+def coarse(got, ref):
+    """Gate A statistic: max|got - ref| / max|ref|."""
+    got, ref = got.detach().double(), ref.detach().double()
+    return float((got - ref).abs().max() / (ref.abs().max() + 1e-300))
+
+
+def _b2_stat(x, ref, dim):
+    rms = ref.pow(2).mean(dim, keepdim=True).sqrt()
+    u = ulp_bf16(torch.maximum(ref.abs(), 0.125 * rms))
+    return ((x - ref) / u).pow(2).mean(dim).sqrt()
+
+
+def gate_b(got, ref, S, T, rounded=True):
+    """The bands of this script.
+
+    Gate A (coarse, every check): max|got - ref| <= tol * max|ref| with tol = 8 x the band of the matching fp16 test -- 8 = 2^-8 / 2^-11, the ratio
+    of the unit roundoffs of bf16 and fp16 (the convention run_bf16_checks.py states).  fp32 outputs whose error does not pass through a stored
+    bf16 intermediate keep the fp16 test's band: fd_attn_bwd_prep, fd_patchify_bwd, fd_crop_resize_bwd, fd_warp_affine_bwd, fd_sum_slabs, the saved
+    P of fd_small_attn_fwd, fd_lora_wgrad*, the GroupNorm statistics; so do ops whose operands are fp32 by the ABI (fd_cfg_dpm_step, fd_adamw_ema).
+
+    Gate B (sharp; fp32 accumulation and ONE rounding to bf16: every fd_gemm path incl. convolutions, fd_lora_wgrad* and fd_attn_bwd_prep, whose
+    fp32 outputs take the fp32 half-ulp in place of the bf16 one and skip B2).  Both parts must hold.
+      B1, elementwise:  |got - ref| <= 0.5 * ulp_bf16(max(|ref|, |got|)) + 2 * T * 2^-24 * S, S the statement on absolute values in fp64
+          (|A||B|^T + |A2||B2|^T + |bias| + |residual|), T the number of summed terms: the standard forward bound of T fp32 additions in any
+          order (T * u * S to first order), doubled because the MFMA's internal summation order and rounding are not specified.
+      B2, per row and per column:  rms((got - ref) / ulp_bf16(max(|ref|, 2^-3 * rms(ref of that row / column)))) <= B2_MARGIN x the same
+          statistic of ref.to(bfloat16) on the same data (about 0.29 = 1 / sqrt(12)).  The floor 2^-3 rms keeps elements that cancelled to
+          nearly zero, whose error is set by the larger terms that made them, from dominating the statistic.
+          Margin: the statistic of the fp32-accumulate emulation (torch fp32 matmul of the bf16 operands + second slab + bias + residual, rounded once)
+          over that of ref.to(bfloat16), largest over rows and columns, measured on the CPU (tests/test_bf16_bands_cpu.py recomputes and prints
+          them) at every GEMM-family K of this script:
+              K      40     64     288    320    336    576    640    1024   1280   2880   4104   5120   11520
+              ratio  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000
+          (the fp32 accumulation error is ~2^-16 of a bf16 ulp-sized step, so the emulation and the rounded reference differ only at near-ties)
+          margin = 1.25 x the largest (1.000) = 1.25; the 1.25 covers another summation order.  It is below 2, so the floor stands.
+
+    Gate C (the other single-rounding ops: norms, softmax, activations, GEGLU, attention outputs, elementwise families): the elementwise maximum of
+    |got - ref| / ulp_bf16(max(|ref|, floor)), floor = 2^-3 * rms(ref) unless the check states another, is printed and held to the value measured
+    on the MI355X + 0.5 ulp (table GATE_C).  The reference rounded once to bf16 scores 0.5 by construction: that is the yardstick, never the
+    kernel's own output.
+
+    Returns a dict: b1_bad (elements over the B1 band), b1_ratio (max |err| / band), b2_row / b2_col (largest ratio to the yardstick; None for
+    fp32 outputs)."""
+    got, ref, S = got.detach().double(), ref.detach().double(), S.detach().double()
+    err = (got - ref).abs()
+    half = 0.5 * ulp_bf16(torch.maximum(ref.abs(), got.abs())) if rounded else 2.0 ** -24 * torch.maximum(ref.abs(), got.abs())
+    band = half + 2.0 * T * 2.0 ** -24 * S
+    ratio = err / band.clamp_min(1e-300)
+    out = dict(b1_bad=int((err > band).sum()), b1_ratio=float(ratio.max()), b2_row=None, b2_col=None)
+    if rounded:
+        r2 = ref.reshape(-1, ref.shape[-1])
+        g2 = got.reshape(r2.shape)
+        yard = ref.to(BF).double().reshape(r2.shape)
+        for key, dim in (("b2_row", 1), ("b2_col", 0)):
+            out[key] = float((_b2_stat(g2, r2, dim) / _b2_stat(yard, r2, dim).clamp_min(0.05)).max())
+    out["ok_b1"] = out["b1_bad"] == 0 and math.isfinite(out["b1_ratio"])
+    out["ok_b2"] = (not rounded) or (out["b2_row"] <= B2_MARGIN and out["b2_col"] <= B2_MARGIN)
+    return out
+
+
+def gate_c_stat(got, ref, floor=None):
+    got, ref = got.detach().double(), ref.detach().double()
+    if floor is None:
+        floor = 0.125 * float(ref.pow(2).mean().sqrt())
+    return float(((got - ref).abs() / ulp_bf16(ref.abs().clamp_min(max(floor, 2.0 ** -126)))).max())
+
+
+# Gate C table: check name -> (value measured on the MI355X in bf16 ulp, gate = measured + 0.5).  Rows over 2 ulp name the source.
+GATE_C = {
+    'attn B2 H8 Tq1024 Tk1024 d40 kv_div1: o': (16.502, 17.002),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq1024 Tk1024 d40 kv_div1: dk': (21.191, 21.691),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq1024 Tk1024 d40 kv_div1: dv': (19.720, 20.220),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq1024 Tk1024 d40 kv_div1: dq': (28.541, 29.041),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H8 Tq1024 Tk1024 d40 kv_div1: o': (13.560, 14.060),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H8 Tq1024 Tk1024 d40 kv_div1: dk': (21.818, 22.318),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H8 Tq1024 Tk1024 d40 kv_div1: dv': (19.747, 20.247),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H8 Tq1024 Tk1024 d40 kv_div1: dq': (18.659, 19.159),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq256 Tk256 d80 kv_div1: o': (13.805, 14.305),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq256 Tk256 d80 kv_div1: dk': (15.301, 15.801),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq256 Tk256 d80 kv_div1: dv': (17.859, 18.359),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H8 Tq256 Tk256 d80 kv_div1: dq': (19.132, 19.632),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B1 H4 Tq64 Tk64 d160 kv_div1: o': (8.407, 8.907),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B1 H4 Tq64 Tk64 d160 kv_div1: dk': (10.750, 11.250),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B1 H4 Tq64 Tk64 d160 kv_div1: dv': (14.004, 14.504),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B1 H4 Tq64 Tk64 d160 kv_div1: dq': (13.082, 13.582),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H4 Tq300 Tk77 d40 kv_div1: o': (9.028, 9.528),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H4 Tq300 Tk77 d40 kv_div1: dk': (14.641, 15.141),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H4 Tq300 Tk77 d40 kv_div1: dv': (12.975, 13.475),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B2 H4 Tq300 Tk77 d40 kv_div1: dq': (14.654, 15.154),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H4 Tq300 Tk77 d40 kv_div1: o': (8.170, 8.670),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H4 Tq300 Tk77 d40 kv_div1: dk': (10.516, 11.016),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H4 Tq300 Tk77 d40 kv_div1: dv': (16.520, 17.020),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B2 H4 Tq300 Tk77 d40 kv_div1: dq': (16.416, 16.916),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B4 H8 Tq1024 Tk13 d40 kv_div2: o': (10.391, 10.891),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn B4 H8 Tq1024 Tk13 d40 kv_div2: dq': (27.851, 28.351),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B4 H8 Tq1024 Tk13 d40 kv_div2: o': (11.580, 12.080),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn (pre-scaled q) B4 H8 Tq1024 Tk13 d40 kv_div2: dq': (31.954, 32.454),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'attn fwd, first key tile far below the rest: o': (13.291, 13.791),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'small attn B1 H2 T1 d32: o': (0.000, 0.500),
+    'small attn B1 H2 T1 d32: dq': (0.000, 0.500),
+    'small attn B1 H2 T1 d32: dk': (0.000, 0.500),
+    'small attn B1 H2 T1 d32: dv': (0.000, 0.500),
+    'small attn B1 H2 T1 d40: o': (0.000, 0.500),
+    'small attn B1 H2 T1 d40: dq': (0.000, 0.500),
+    'small attn B1 H2 T1 d40: dk': (0.000, 0.500),
+    'small attn B1 H2 T1 d40: dv': (0.000, 0.500),
+    'small attn B1 H2 T1 d64: o': (0.000, 0.500),
+    'small attn B1 H2 T1 d64: dq': (0.000, 0.500),
+    'small attn B1 H2 T1 d64: dk': (0.000, 0.500),
+    'small attn B1 H2 T1 d64: dv': (0.000, 0.500),
+    'small attn B1 H2 T63 d32: o': (0.500, 1.000),
+    'small attn B1 H2 T63 d32: dq': (0.500, 1.000),
+    'small attn B1 H2 T63 d32: dk': (0.500, 1.000),
+    'small attn B1 H2 T63 d32: dv': (0.500, 1.000),
+    'small attn B1 H2 T63 d40: o': (0.500, 1.000),
+    'small attn B1 H2 T63 d40: dq': (0.500, 1.000),
+    'small attn B1 H2 T63 d40: dk': (0.500, 1.000),
+    'small attn B1 H2 T63 d40: dv': (0.500, 1.000),
+    'small attn B1 H2 T63 d64: o': (0.500, 1.000),
+    'small attn B1 H2 T63 d64: dq': (0.500, 1.000),
+    'small attn B1 H2 T63 d64: dk': (0.500, 1.000),
+    'small attn B1 H2 T63 d64: dv': (0.500, 1.000),
+    'small attn B1 H2 T64 d32: o': (0.500, 1.000),
+    'small attn B1 H2 T64 d32: dq': (0.500, 1.000),
+    'small attn B1 H2 T64 d32: dk': (0.500, 1.000),
+    'small attn B1 H2 T64 d32: dv': (0.500, 1.000),
+    'small attn B1 H2 T64 d40: o': (0.500, 1.000),
+    'small attn B1 H2 T64 d40: dq': (0.500, 1.000),
+    'small attn B1 H2 T64 d40: dk': (0.500, 1.000),
+    'small attn B1 H2 T64 d40: dv': (0.500, 1.000),
+    'small attn B1 H2 T64 d64: o': (0.500, 1.000),
+    'small attn B1 H2 T64 d64: dq': (0.500, 1.000),
+    'small attn B1 H2 T64 d64: dk': (0.500, 1.000),
+    'small attn B1 H2 T64 d64: dv': (0.500, 1.000),
+    'small attn B1 H2 T65 d32: o': (0.500, 1.000),
+    'small attn B1 H2 T65 d32: dq': (0.500, 1.000),
+    'small attn B1 H2 T65 d32: dk': (0.500, 1.000),
+    'small attn B1 H2 T65 d32: dv': (0.500, 1.000),
+    'small attn B1 H2 T65 d40: o': (0.500, 1.000),
+    'small attn B1 H2 T65 d40: dq': (0.500, 1.000),
+    'small attn B1 H2 T65 d40: dk': (0.500, 1.000),
+    'small attn B1 H2 T65 d40: dv': (0.500, 1.000),
+    'small attn B1 H2 T65 d64: o': (0.500, 1.000),
+    'small attn B1 H2 T65 d64: dq': (0.500, 1.000),
+    'small attn B1 H2 T65 d64: dk': (0.500, 1.000),
+    'small attn B1 H2 T65 d64: dv': (0.500, 1.000),
+    'small attn B1 H2 T77 d32: o': (0.500, 1.000),
+    'small attn B1 H2 T77 d32: dq': (0.500, 1.000),
+    'small attn B1 H2 T77 d32: dk': (0.500, 1.000),
+    'small attn B1 H2 T77 d32: dv': (0.500, 1.000),
+    'small attn B1 H2 T77 d40: o': (0.500, 1.000),
+    'small attn B1 H2 T77 d40: dq': (0.500, 1.000),
+    'small attn B1 H2 T77 d40: dk': (0.500, 1.000),
+    'small attn B1 H2 T77 d40: dv': (0.500, 1.000),
+    'small attn B2 H12 T77 d64: o': (0.500, 1.000),
+    'small attn B2 H12 T77 d64: dq': (0.501, 1.001),
+    'small attn B2 H12 T77 d64: dk': (0.500, 1.000),
+    'small attn B2 H12 T77 d64: dv': (0.500, 1.000),
+    'small attn B1 H2 T128 d32: o': (0.500, 1.000),
+    'small attn B1 H2 T128 d32: dq': (0.500, 1.000),
+    'small attn B1 H2 T128 d32: dk': (0.500, 1.000),
+    'small attn B1 H2 T128 d32: dv': (0.500, 1.000),
+    'small attn B1 H2 T128 d40: o': (0.500, 1.000),
+    'small attn B1 H2 T128 d40: dq': (0.500, 1.000),
+    'small attn B1 H2 T128 d40: dk': (0.500, 1.000),
+    'small attn B1 H2 T128 d40: dv': (0.500, 1.000),
+    'small attn B1 H2 T128 d64: o': (0.500, 1.000),
+    'small attn T128 d128: o': (0.500, 1.000),
+    'cross block C320 B2 HW64 L5 kv_div1 r0: y': (7.978, 8.478),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B2 HW64 L5 kv_div1 r0: LayerNorm3(y)': (7.707, 8.207),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B4 HW1024 L77 kv_div2 r0: y': (3.973, 4.473),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B4 HW1024 L77 kv_div2 r0: LayerNorm3(y)': (5.362, 5.862),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C640 B2 HW64 L80 kv_div1 r0: y': (3.615, 4.115),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C640 B2 HW64 L80 kv_div1 r0: LayerNorm3(y)': (4.027, 4.527),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B2 HW64 L5 kv_div1 r4: n2': (0.500, 1.000),
+    'cross block C320 B2 HW64 L5 kv_div1 r4: y': (8.595, 9.095),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B2 HW64 L5 kv_div1 r4: o': (15.306, 15.806),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B4 HW1024 L77 kv_div2 r4: n2': (0.500, 1.000),
+    'cross block C320 B4 HW1024 L77 kv_div2 r4: y': (7.406, 7.906),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B4 HW1024 L77 kv_div2 r4: o': (43.737, 44.237),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C640 B2 HW64 L80 kv_div1 r16: n2': (0.500, 1.000),
+    'cross block C640 B2 HW64 L80 kv_div1 r16: y': (10.389, 10.889),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C640 B2 HW64 L80 kv_div1 r16: o': (32.607, 33.107),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B4 HW1024 L77 kv_div2 r16: n2': (0.500, 1.000),
+    'cross block C320 B4 HW1024 L77 kv_div2 r16: y': (13.664, 14.164),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'cross block C320 B4 HW1024 L77 kv_div2 r16: o': (55.478, 55.978),        # P stored in bf16 before the PV product; q pre-scaled and re-rounded where d = 40; __expf / exp2
+    'conv_up2 phases 3x40^2 128->512': (10.228, 10.728),        # phase weights are sums of up to four taps rounded to bf16 once more (second stored rounding)
+    'conv_up2 phases dgrad 3x40^2 128->512': (10.105, 10.605),        # phase weights are sums of up to four taps rounded to bf16 once more (second stored rounding)
+    'conv_up2 phases 5x16^2 1280->1280': (13.050, 13.550),        # phase weights are sums of up to four taps rounded to bf16 once more (second stored rounding)
+    'conv_up2 phases dgrad 5x16^2 1280->1280': (13.462, 13.962),        # phase weights are sums of up to four taps rounded to bf16 once more (second stored rounding)
+    'gemm epilogue silu + rowbias + residual': (0.500, 1.000),        # 3.990 while the staged epilogue rounded before and after the residual
+    'gemm epilogue quick_gelu': (0.500, 1.000),
+    'fused geglu 300x64x64: activation': (0.500, 1.000),
+    'fused geglu 4100x1280x320: activation': (0.500, 1.000),
+    'geglu interleaved backward vs fp64': (0.500, 1.000),
+    'groupnorm B2 HW256 C320+0 silu=1: fwd': (0.500, 1.000),
+    'groupnorm B2 HW256 C320+0 silu=1: bwd dx1': (0.500, 1.000),
+    'groupnorm B3 HW64 C1280+640 silu=1: fwd': (0.500, 1.000),
+    'groupnorm B3 HW64 C1280+640 silu=1: bwd dx1': (0.500, 1.000),
+    'groupnorm B3 HW64 C1280+640 silu=1: bwd dx2': (0.500, 1.000),
+    'groupnorm B2 HW100 C640+320 silu=0: fwd': (0.500, 1.000),
+    'groupnorm B2 HW100 C640+320 silu=0: bwd dx1': (0.500, 1.000),
+    'groupnorm B2 HW100 C640+320 silu=0: bwd dx2': (0.500, 1.000),
+    'groupnorm B2 HW1024 C320+0 silu=1: fwd': (0.500, 1.000),
+    'groupnorm B2 HW1024 C320+0 silu=1: bwd dx1': (0.500, 1.000),
+    'groupnorm_fwd_stats B4 HW4096 C320': (0.500, 1.000),
+    'layernorm 333x1280: fwd': (0.500, 1.000),
+    'layernorm 333x1280: bwd + add': (0.500, 1.000),
+    'layernorm 64x768: fwd': (0.500, 1.000),
+    'layernorm 64x768: bwd + add': (0.500, 1.000),
+    'layernorm 2048x320: fwd': (0.500, 1.000),
+    'layernorm 2048x320: bwd + add': (0.500, 1.000),
+    'softmax cols=1': (0.000, 0.500),
+    'softmax bwd cols=1 (from the stored p)': (0.000, 0.500),
+    'softmax cols=7': (0.500, 1.000),
+    'softmax bwd cols=7 (from the stored p)': (0.500, 1.000),
+    'softmax cols=255': (0.500, 1.000),
+    'softmax bwd cols=255 (from the stored p)': (0.500, 1.000),
+    'softmax cols=256': (0.500, 1.000),
+    'softmax bwd cols=256 (from the stored p)': (0.500, 1.000),
+    'softmax cols=257': (0.500, 1.000),
+    'softmax bwd cols=257 (from the stored p)': (0.500, 1.000),
+    'softmax cols=4095': (0.500, 1.000),
+    'softmax bwd cols=4095 (from the stored p)': (0.500, 1.000),
+    'softmax cols=4096': (0.500, 1.000),
+    'softmax bwd cols=4096 (from the stored p)': (0.500, 1.000),
+    'softmax masked': (0.500, 1.000),
+    'geglu fwd': (0.500, 1.000),
+    'geglu bwd': (0.500, 1.000),
+    'geglu bwd interleaved': (0.500, 1.000),
+    'act silu n=8396619': (0.500, 1.000),
+    'act_bwd silu n=8396619': (0.500, 1.000),
+    'act silu n=11': (0.472, 0.972),
+    'act_bwd silu n=11': (0.473, 0.973),
+    'act relu n=8396619': (0.000, 0.500),
+    'act_bwd relu n=8396619': (0.000, 0.500),
+    'act relu n=11': (0.000, 0.500),
+    'act_bwd relu n=11': (0.000, 0.500),
+    'act hardswish n=8396619': (0.500, 1.000),
+    'act_bwd hardswish n=8396619': (0.500, 1.000),
+    'act hardswish n=11': (0.435, 0.935),
+    'act_bwd hardswish n=11': (0.250, 0.750),
+    'act hardsigmoid n=8396619': (0.500, 1.000),
+    'act_bwd hardsigmoid n=8396619': (0.333, 0.833),
+    'act hardsigmoid n=11': (0.333, 0.833),
+    'act_bwd hardsigmoid n=11': (0.333, 0.833),
+    'act quick_gelu n=8396619': (0.500, 1.000),
+    'act_bwd quick_gelu n=8396619': (0.500, 1.000),
+    'act quick_gelu n=11': (0.450, 0.950),
+    'act_bwd quick_gelu n=11': (0.452, 0.952),
+    'act gelu n=8396619': (0.498, 0.998),
+    'act_bwd gelu n=8396619': (0.500, 1.000),
+    'act gelu n=11': (0.325, 0.825),
+    'act_bwd gelu n=11': (0.458, 0.958),
+    'add': (0.500, 1.000),
+    'add b=None': (0.500, 1.000),
+    'add n=11': (0.469, 0.969),
+    'downsum2x2': (0.500, 1.000),
+    'small conv s1': (0.500, 1.000),
+    'small conv bwd s1': (0.002, 0.502),
+    'small conv s2': (0.500, 1.000),
+    'small conv bwd s2': (0.001, 0.501),
+    'small conv fast path 4->320 64x64 s1 none nchw': (0.500, 1.000),
+    'small conv fast path 3->16 45x37 s2 hardswish nchw': (0.500, 1.000),
+    'small conv fast path 4->512 18x22 s1 none nhwc': (0.500, 1.000),
+    '1x1 conv': (0.499, 0.999),
+    'dwconv k3s1': (0.500, 1.000),
+    'dwconv bwd k3s1': (0.500, 1.000),
+    'dwconv k3s2': (0.500, 1.000),
+    'dwconv bwd k3s2': (0.500, 1.000),
+    'dwconv k5s1': (0.500, 1.000),
+    'dwconv bwd k5s1': (0.500, 1.000),
+    'dwconv k5s2': (0.500, 1.000),
+    'dwconv bwd k5s2': (0.500, 1.000),
+    'avgpool': (0.494, 0.994),
+    'scale_channels': (0.500, 1.000),
+    'scale_channels dx': (0.500, 1.000),
+    'scale_channels ds': (0.498, 0.998),
+    'avgpool bwd': (0.490, 0.990),
+    'crop_resize 512->224 (six boxes)': (0.719, 1.219),
+    'crop_resize_u8 48x64->28 (seven boxes)': (0.513, 1.013),
+    'warp_affine 512->112': (0.670, 1.170),
+}
+
+# ============================================================================= plumbing
+FAILS, SEEN_C = [], set()
+dev = ops = layers = lib = None
+
+
+def _init():
+    global dev, ops, layers, lib
+    assert os.environ.get("FD_DTYPE") == "bf16", "run with FD_DTYPE=bf16"
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.dirname(HERE))
+    from finetune_fair_diffusion_amd import layers as _layers, lib as _lib, ops as _ops
+    ops, layers, lib = _ops, _layers, _lib
+    dev = torch.device("cuda:0")
+    assert lib.get().fd_working_dtype().decode() == "bf16" and ops.F16 == BF
+
+
+def fail(msg):
+    print("  FAIL:", msg)
+    FAILS.append(msg)
+
+
+def X(name, cond, msg=""):
+    """An exact property (bit equality, a dispatch, a sentinel)."""
+    if not cond:
+        fail(f"{name}: {msg or 'property does not hold'}")
+    else:
+        print(f"[{name}] ok")
+
+
+def A(name, got, ref, tol, legacy=None):
+    e = coarse(got, ref)
+    print(f"[A {name}] rel max err {e:.3e} (tol {tol:.1e}{'' if legacy is None else f', former kernels() band {legacy:.1e}'})")
+    if not (math.isfinite(e) and e <= tol and (legacy is None or e <= legacy)):
+        fail(f"{name}: gate A {e:.3e} > {tol:.1e}")
+
+
+def B(name, got, ref, S, T, tol, legacy=None):
+    A(name, got, ref, tol, legacy)
+    rounded = got.dtype == BF
+    r = gate_b(got, ref, S, T, rounded)
+    b2 = f"B2 row {r['b2_row']:.3f} col {r['b2_col']:.3f} (margin {B2_MARGIN})" if rounded else "B2 n/a (fp32 output)"
+    print(f"[B {name}] B1 max ratio {r['b1_ratio']:.3f}, {r['b1_bad']} elements over; {b2}")
+    if not r["ok_b1"]:
+        fail(f"{name}: gate B1, {r['b1_bad']} elements over the band (max ratio {r['b1_ratio']:.3f})")
+    if not r["ok_b2"]:
+        fail(f"{name}: gate B2 row {r['b2_row']:.3f} col {r['b2_col']:.3f} > {B2_MARGIN}")
+
+
+def Cv(name, value):
+    """Gate C on a statistic already computed (the maximum over the variants of one check)."""
+    assert name not in SEEN_C, name
+    SEEN_C.add(name)
+    row = GATE_C.get(name)
+    print(f"[C {name}] max err {value:.3f} bf16 ulp (gate {row[1] if row else 'MISSING'})")
+    if row is None:
+        fail(f"{name}: no row in GATE_C (measured {value:.3f})")
+    elif not (math.isfinite(value) and value <= row[1]):
+        fail(f"{name}: gate C {value:.3f} ulp > {row[1]}")
+
+
+def C(name, got, ref, tol, floor=None, legacy=None):
+    A(name, got, ref, tol, legacy)
+    Cv(name, gate_c_stat(got, ref, floor))
+
+
+def rnd(*shape, seed, scale=1.0, dtype=BF):
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    return (torch.randn(*shape, generator=g) * scale).to(dev).to(dtype)
+
+
+def bits16(t):
+    return t.contiguous().view(torch.int16)
+
+
+def bit_equal(name, got, ref):
+    """Bit equality, NaN compared as NaN (payloads may differ), the sign of zero significant."""
+    if got.shape != ref.shape or got.dtype != ref.dtype:
+        return fail(f"{name}: shape / dtype {got.shape} {got.dtype} vs {ref.shape} {ref.dtype}")
+    gn, rn = torch.isnan(got), torch.isnan(ref)
+    view = (lambda t: t.contiguous().view(torch.int16)) if got.element_size() == 2 else (lambda t: t.contiguous().view(torch.int32))
+    diff = ((view(got) != view(ref)) & ~rn) | (gn != rn)
+    if bool(diff.any()):
+        i = int(diff.flatten().nonzero()[0])
+        return fail(f"{name}: {int(diff.sum())} elements differ; first at {i}: got {got.flatten()[i].item()!r}, want {ref.flatten()[i].item()!r}")
+    print(f"[{name}] bit-exact over {got.numel()} elements")
+
+
+def desc(M, N, K, K2=0, batch=1):
+    d = lib.GemmDesc()
+    d.M, d.N, d.K, d.K2, d.batch, d.ldc, d.lda, d.ldb, d.alpha = M, N, K, K2, batch, N, K, K, 1.0
+    ws = ops.gemm_workspace()
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    if K2:
+        d.A2, d.B2, d.lda2, d.ldb2 = ws.data_ptr(), ws.data_ptr(), K2, K2
+    return d
+
+
+def kernel_name(d):
+    buf = ctypes.create_string_buffer(128)
+    split = lib.get().fd_gemm_kernel_name(ctypes.byref(d), buf, 128)
+    return buf.value.decode(), split
+
+
+def tile_of(d):
+    return lib.get().fd_gemm_tile(ctypes.byref(d))
+
+
+# ============================================================================= gemm
+def _gemm_full(tag, M, N, K, K2, want_tile=None, want_name=None, want_split=False, poison=False, legacy=None, operands=True):
+    """a.b^T (+ second slab K2, fp32 bias, bf16 residual) against fp64, gates A and B; the dispatch asserted through the host-only queries."""
+    a, b = rnd(M, K, seed=1), rnd(N, K, scale=0.1, seed=2)
+    a2, b2 = (rnd(M, K2, seed=3), rnd(N, K2, seed=4)) if K2 else (None, None)
+    bias, res = (rnd(N, dtype=torch.float32, seed=5), rnd(M, N, seed=6)) if operands else (None, None)
+    d = desc(M, N, K, K2)
+    if operands:
+        d.bias, d.residual, d.ldr = bias.data_ptr(), res.data_ptr(), N
+    name, split = kernel_name(d)
+    tile = tile_of(d)
+    ok = (want_tile is None or tile % 1000000 == want_tile) and (want_name is None or name.startswith(want_name)) and ((split > 1) == want_split)
+    X(f"{tag}: dispatch", ok, f"kernel {name!r} tile {tile} split {split}; wanted {want_name!r} {want_tile} split={want_split}")
+    aa = a
+    if poison:          # the operand sits inside a larger buffer whose other bytes are huge: a lane that read past its row would show
+        wide = torch.full((M + 8, K + 64), 6e4, dtype=BF, device=dev)
+        wide[:M, :K] = a
+        aa = wide[:M, :K]
+    c = ops.gemm(aa, b, a2=a2, b2=b2, bias=bias, residual=res)
+    ref = a.double() @ b.double().t()
+    S = a.double().abs() @ b.double().abs().t()
+    if K2:
+        ref += a2.double() @ b2.double().t()
+        S += a2.double().abs() @ b2.double().abs().t()
+    if operands:
+        ref += bias.double() + res.double()
+        S += bias.double().abs() + res.double().abs()
+    B(f"{tag} {M}x{N}x{K}+{K2} [{name.split('(')[0][:40]}]", c, ref, S, K + K2 + 2, 8 * 2e-3, legacy)
+    if operands:        # the same launch without the residual: one rounding on every epilogue path (see RESIDUAL FINDING in the module docstring)
+        c1 = ops.gemm(aa, b, a2=a2, b2=b2, bias=bias)
+        B(f"{tag} {M}x{N}x{K}+{K2} without residual", c1, ref - res.double(), S - res.double().abs(), K + K2 + 1, 8 * 2e-3)
+    torch.cuda.synchronize()
+
+
+def gemm():
+    for M, N, K in [(128, 128, 64), (300, 320, 320), (65, 1280, 40)]:
+        _gemm_full("gemm glds", M, N, K, 8, want_name="gemm_glds")
+    _gemm_full("gemm big", 6200, 1280, 328, 8, want_tile=256320)
+    _gemm_full("gemm big", 2600, 1280, 328, 8, want_tile=128320)
+    _gemm_full("gemm big", 6800, 480, 1024, 8, want_tile=128160)
+    _gemm_full("gemm big", 25400, 512, 328, 8, want_tile=256256)
+    _gemm_full("gemm big", 17000, 384, 328, 8, want_tile=256128)
+    _gemm_full("gemm big", 204400, 128, 320, 8, want_tile=512128)
+    _gemm_full("gemm split-K", 1024, 1280, 4104, 8, want_tile=128320, want_split=True)
+    _gemm_full("gemm split-K", 1000, 320, 5120, 8, want_tile=128160, want_split=True)
+    _gemm_full("gemm ping-pong", 3100, 2560, 320, 8, want_name="gemm_pp_kernel<256, 0", poison=True)
+    _gemm_full("gemm ping-pong", 3300, 2560, 328, 0, want_name="gemm_pp_kernel<256, 0", poison=True)
+    # the two GEMMs of the former kernels() of run_bf16_checks.py, at its band
+    _gemm_full("gemm (former kernels())", 4096, 320, 1280, 0, want_split=True, legacy=1e-2, operands=False)
+    _gemm_full("gemm (former kernels())", 65536, 320, 320, 0, want_tile=256320, legacy=1e-2)
+    # skinny: LoRA down-projection shapes, one wave per 16 rows, K split over KS waves; A a column slice of a wider matrix; plain operands
+    for M, N, K in [(1030, 8, 320), (1030, 24, 640), (1030, 56, 1280)]:
+        wide = rnd(M, K + 64, seed=1)
+        a, b = wide[:, 32:32 + K], rnd(N, K, scale=0.1, seed=2)
+        d = desc(M, N, K)
+        X(f"gemm skinny {M}x{N}x{K}: dispatch", tile_of(d) == 16000 + (N + 15) // 16 * 16, str(tile_of(d)))
+        out = torch.full((M, N + 8), 7.0, dtype=BF, device=dev)
+        c = ops.gemm(a, b, out=out[:, :N])
+        B(f"gemm skinny {M}x{N}x{K}", c, a.double() @ b.double().t(), a.double().abs() @ b.double().abs().t(), K, 8 * 2e-3)
+        X(f"gemm skinny {M}x{N}x{K}: nothing written beyond N", bool((out[:, N:] == 7.0).all()))
+    # batched patch embedding: rows 1..256 of every sample's [264, N] buffer; sentinel rows untouched
+    Z, N, rows, K, Tp = 3, 768, 256, 592, 264
+    a, w = rnd(Z * rows, K, seed=1), rnd(N, K, scale=0.05, seed=2)
+    bias, pos = rnd(N, dtype=torch.float32, seed=3), rnd(rows, N, seed=4)
+    x = torch.full((Z, Tp, N), -7.0, dtype=BF, device=dev)
+    ops.gemm_batched_into(a, w, x[:, 1:rows + 1], bias, pos, Z, rows)
+    ref = a.double().view(Z, rows, K) @ w.double().t() + bias.double() + pos.double()
+    S = a.double().abs().view(Z, rows, K) @ w.double().abs().t() + bias.double().abs() + pos.double().abs()
+    B("gemm_batched_into Z=3 N=768", x[:, 1:rows + 1].contiguous(), ref, S, K + 2, 8 * 2e-3)
+    X("gemm_batched_into: sentinel rows", bool((x[:, 0] == -7.0).all()) and bool((x[:, rows + 1:] == -7.0).all()))
+    buf, wT = rnd(Z, Tp, N, seed=5), rnd(K, N, scale=0.05, seed=6)
+    got = ops.gemm_batched_from(buf[:, 1:rows + 1], wT, Z, rows)
+    B("gemm_batched_from Z=3 D=768", got.view(Z, rows, K), buf[:, 1:rows + 1].double() @ wT.double().t(),
+      buf[:, 1:rows + 1].double().abs() @ wT.double().abs().t(), N, 8 * 2e-3)
+    a, b = rnd(6, 200, 64, seed=1), rnd(6, 136, 64, seed=2)
+    B("bgemm", ops.bgemm(a, b, alpha=0.25), 0.25 * torch.einsum("zmk,znk->zmn", a.double(), b.double()),
+      0.25 * torch.einsum("zmk,znk->zmn", a.double().abs(), b.double().abs()), 65, 8 * 2e-3)
+    # epilogue activations on the accumulator (gate C: the activation follows the sum)
+    M, N, K, R = 777, 640, 320, 8
+    a, b, a2, b2 = rnd(M, K, seed=1), rnd(N, K, scale=0.1, seed=2), rnd(M, R, seed=3), rnd(N, R, seed=4)
+    bias, res, rb = rnd(N, dtype=torch.float32, seed=5), rnd(M, N, seed=6), rnd(7, N, seed=7)
+    z = a.double() @ b.double().t() + a2.double() @ b2.double().t() + bias.double() + rb.double().repeat_interleave(111, 0)
+    C("gemm epilogue silu + rowbias + residual", ops.gemm(a, b, a2=a2, b2=b2, bias=bias, rowbias=rb, rows_per_batch=111, residual=res, act="silu"),
+      F.silu(z) + res.double(), 8 * 2e-3)
+    A("gemm f32 out gelu", ops.gemm(a, b, bias=bias, alpha=0.5, out_dtype=torch.float32, act="gelu"), F.gelu(0.5 * (a.double() @ b.double().t()) + bias.double()), 1e-3)
+    z = a.double() @ b.double().t()
+    C("gemm epilogue quick_gelu", ops.gemm(a, b, act="quick_gelu"), z * torch.sigmoid(1.702 * z), 8 * 2e-3)
+    # column scale (the q third of the stacked q / k / v projection): fp32 epilogue, before bias and rounding; other columns bit-identical
+    for M, N, K, cols in [(300, 320, 320, 320), (2048, 2560, 320, 640)]:
+        a, b, a2, b2 = rnd(M, K, seed=1), rnd(N, K, scale=0.1, seed=2), rnd(M, 8, seed=3), rnd(N, 8, seed=4)
+        fac = 0.2280966
+        f32 = float(torch.tensor(fac, dtype=torch.float32))
+        plain, c = ops.gemm(a, b, a2=a2, b2=b2), ops.gemm(a, b, a2=a2, b2=b2, colscale=(fac, cols))
+        X(f"colscale {M}x{N}: other columns bit-identical", torch.equal(c[:, cols:], plain[:, cols:]))
+        ref = a.double() @ b.double().t() + a2.double() @ b2.double().t()
+        S = a.double().abs() @ b.double().abs().t() + a2.double().abs() @ b2.double().abs().t()
+        ref[:, :cols] *= f32
+        S[:, :cols] *= f32
+        B(f"gemm colscale {M}x{N}x{K} cols {cols}", c, ref, S, K + 8 + 1, 8 * 2e-3)
+        bias, res = rnd(N, dtype=torch.float32, seed=5), rnd(M, N, seed=6)
+        ref2, S2 = a.double() @ b.double().t(), a.double().abs() @ b.double().abs().t()
+        ref2[:, :cols] *= f32
+        S2[:, :cols] *= f32
+        B(f"gemm colscale + bias + residual {M}x{N}", ops.gemm(a, b, bias=bias, residual=res, colscale=(fac, cols)), ref2 + bias.double() + res.double(),
+          S2 + bias.double().abs() + res.double().abs(), K + 3, 8 * 2e-3)
+    # fused GEGLU == projection followed by fd_geglu_fwd, bit for bit (both halves rounded to bf16 before the gate in either path)
+    for M, Fh, K in [(300, 64, 64), (4100, 1280, 320)]:
+        a, w, bias = rnd(M, K, seed=1), rnd(2 * Fh, K, scale=0.1, seed=2), rnd(2 * Fh, dtype=torch.float32, seed=3)
+        proj = ops.gemm(a, w, bias=bias)
+        ref = ops.geglu(proj)
+        wi, bi = ops.interleave_geglu(w, bias)
+        got = ops.gemm(a, wi, bias=bi, act="geglu")
+        X(f"fused geglu {M}x{Fh}x{K}: bit-identical to the unfused path", got.shape == (M, Fh) and torch.equal(got, ref))
+        x = a.double() @ w.double().t() + bias.double()
+        A(f"fused geglu {M}x{Fh}x{K} vs fp64", got, x[:, :Fh] * F.gelu(x[:, Fh:]), 8 * 5e-3)
+        # gate C on the activation alone: the gate applied to the halves as stored
+        C(f"fused geglu {M}x{Fh}x{K}: activation", got, proj[:, :Fh].double() * F.gelu(proj[:, Fh:].double()), 8 * 2e-3)
+    aux = torch.empty(M, 2 * Fh, dtype=BF, device=dev)
+    gg = ops.gemm(a, wi, bias=bi, act="geglu", aux=aux)
+    X("fused geglu with pre-gate output", torch.equal(gg, ref) and torch.equal(aux[:, 0::2], proj[:, :Fh]) and torch.equal(aux[:, 1::2], proj[:, Fh:]))
+    dy = rnd(M, Fh, seed=4)
+    d_il, d_ref = ops.geglu_bwd_interleaved(aux, dy), ops.geglu_bwd(proj, dy)
+    X("geglu interleaved backward == fd_geglu_bwd", torch.equal(d_il[:, 0::2], d_ref[:, :Fh]) and torch.equal(d_il[:, 1::2], d_ref[:, Fh:]))
+    pr = proj.double().requires_grad_(True)
+    (pr[:, :Fh] * F.gelu(pr[:, Fh:])).backward(dy.double())
+    C("geglu interleaved backward vs fp64", torch.cat([d_il[:, 0::2], d_il[:, 1::2]], 1), pr.grad, 8 * 3e-3)
+    _gn_stats_epilogue()
+
+
+def _unit_sums(c, rows=32):
+    """fp64 statement of fd_gemm_desc.gn_stats: per 32-row chunk and 10-channel unit the (sum, sum of squares) of the stored values."""
+    M, N = c.shape
+    pad = (-M) % rows
+    x = torch.cat([c.double(), torch.zeros(pad, N, dtype=torch.float64, device=c.device)]).reshape((M + pad) // rows, rows, N // 10, 10)
+    return torch.stack([x.sum((1, 3)), (x * x).sum((1, 3))], -1)
+
+
+def _gn_stats_epilogue():
+    """The producer of a GroupNorm's input leaves per-chunk sums of the values it STORED (fp32, the fp16 test's band unchanged); the output is
+    bit-identical to the launch without statistics; the statistics do not depend on the tile policy."""
+    M, N, K = 32768, 320, 320
+    a, b, bias, res = rnd(M, K, seed=1), rnd(N, K, scale=0.1, seed=2), rnd(N, dtype=torch.float32, seed=5), rnd(M, N, seed=6)
+    Bn, H, Cin, Cout = 7, 64, 64, 320
+    x, w = rnd(Bn * H * H, Cin, seed=1), rnd(Cout, 9 * Cin, scale=0.05, seed=2)
+    cb, rb = rnd(Cout, dtype=torch.float32, seed=3), rnd(1, Cout, seed=4)
+    for kind, run in (("dense 32768x320x320", lambda st: ops.gemm(a, b, bias=bias, residual=res, gn_stats=st)),
+                      ("conv 7x64^2 64->320", lambda st: ops.conv3x3(x, w, Bn, H, H, bias=cb, rowbias=rb, gn_stats=st)[0])):
+        plain, c = run(False), run(True)
+        st = getattr(c, "gn_stats", None)
+        X(f"gn_stats {kind}: output bit-identical, statistics present", torch.equal(plain, c) and st is not None and st[1] == 32)
+        if st is None:
+            continue
+        ref = _unit_sums(c)
+        err = float(((st[0].double() - ref).abs() / (ref.abs() + 1.0)).max())
+        print(f"[A gn_stats {kind}] max err {err:.2e} (tol 2.0e-05)")
+        X(f"gn_stats {kind}: sums of the stored values", st[0].shape == ref.shape and err < 2e-5, f"{err:.2e}")
+        X(f"gn_stats {kind}: fixed order", torch.equal(run(True).gn_stats[0], st[0]))
+    M, Ms, N, K = 32768, 8192, 640, 640
+    a, b, res = rnd(M, K, seed=1), rnd(N, K, scale=0.1, seed=2), rnd(M, N, seed=3)
+    tiles = [tile_of(desc(m, N, K)) for m in (M, Ms)]
+    X("gn_stats tile policy: dispatch", tiles == [256320, 128320], str(tiles))
+    big, small = ops.gemm(a, b, residual=res, gn_stats=True), ops.gemm(a[:Ms], b, residual=res[:Ms], gn_stats=True)
+    X("gn_stats do not depend on the tile policy", torch.equal(big[:Ms], small) and torch.equal(big.gn_stats[0][:Ms // 32], small.gn_stats[0]))
+
+
+# ============================================================================= conv
+def _nhwc(x):
+    Bn, Cc, H, W = x.shape
+    return x.permute(0, 2, 3, 1).reshape(Bn * H * W, Cc).contiguous()
+
+
+def _nchw(y, Bn, H, W):
+    return y.reshape(Bn, H, W, -1).permute(0, 3, 1, 2)
+
+
+def conv_ref(x, w, bias=None, stride=1, up=False):
+    """3x3 convolution, padding 1, as unfold + matmul in the dtype of its arguments (fp64): x [B, Cin, H, W], w [Cout, Cin, 3, 3]."""
+    if up:
+        x = F.interpolate(x, scale_factor=2, mode="nearest")
+    Bn, Cin, H, W = x.shape
+    cols = F.unfold(x, 3, padding=1, stride=stride)
+    y = w.reshape(w.shape[0], -1) @ cols
+    Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+    y = y.view(Bn, -1, Ho, Wo)
+    return y if bias is None else y + bias[None, :, None, None]
+
+
+def _conv_pair(x, w, bias=None, **kw):
+    """(reference, S) of the statement and of the statement on absolute values."""
+    return conv_ref(x.double(), w.double(), None if bias is None else bias.double(), **kw), \
+        conv_ref(x.double().abs(), w.double().abs(), None if bias is None else bias.double().abs(), **kw)
+
+
+def _conv_desc(Bn, H, Cin, Cout):
+    d = desc(Bn * H * H, Cout, 9 * Cin)
+    d.conv, d.conv_mode, d.Bn, d.H, d.W, d.Cin, d.Ho, d.Wo, d.lda, d.ldb = 1, 0, Bn, H, H, Cin, H, H, Cin, 9 * Cin
+    return d
+
+
+def conv():
+    for Bn, H, Cin, Cout in [(2, 16, 64, 96), (3, 8, 320, 320), (1, 32, 32, 4)]:
+        x, w, bias = rnd(Bn, Cin, H, H, seed=1), rnd(Cout, Cin, 3, 3, scale=0.05, seed=2), rnd(Cout, dtype=torch.float32, seed=3)
+        wk = w.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous()
+        tag = f"conv {Bn}x{H}^2 {Cin}->{Cout}"
+        for mname, mode, kw in (("normal", ops.CONV_NORMAL, {}), ("stride2", ops.CONV_STRIDE2, dict(stride=2)), ("up2", ops.CONV_UP2, dict(up=True))):
+            y, Ho, Wo = ops.conv3x3(_nhwc(x), wk, Bn, H, H, mode=mode, bias=bias)
+            ref, S = _conv_pair(x, w, bias, **kw)
+            B(f"{tag} {mname}", _nchw(y, Bn, Ho, Wo), ref, S, 9 * Cin + 1, 8 * 2e-3)
+        if Cout % 32 == 0:      # data gradients: flipped / transposed weights [Cin, (ky, kx, co)]
+            wd = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cin, 9 * Cout).contiguous()
+            for mname, stride, mode, hin in (("dgrad", 1, ops.CONV_NORMAL, H), ("stride2 dgrad", 2, ops.CONV_TRANS2, H // 2)):
+                g = rnd(Bn, Cout, H // stride, H // stride, seed=4 + stride)
+                grads = []
+                for xx, ww, gg in ((x.double(), w.double(), g.double()), (x.double().abs(), w.double().abs(), g.double().abs())):
+                    xx = xx.clone().requires_grad_(True)
+                    conv_ref(xx, ww, stride=stride).backward(gg)
+                    grads.append(xx.grad)
+                dx, Ho, Wo = ops.conv3x3(_nhwc(g), wd, Bn, hin, hin, mode=mode)
+                B(f"{tag} {mname}", _nchw(dx, Bn, Ho, Wo), grads[0], grads[1], 9 * Cout, 8 * 2e-3)
+    # halo-staged stride-1 convolutions, each at the smallest batch the dispatcher accepts; one big-tile convolution that is not halo (64 -> 128);
+    # a split-K convolution at 8^2; the convolution of the former kernels()
+    for Bn, H, Cin, Cout, kernel, split, mode, legacy in [(7, 64, 64, 320, "conv_halo_kernel<256, 64", False, 0, None), (13, 32, 64, 640, "conv_halo_kernel<256, 32", False, 0, None),
+                                                        (25, 16, 64, 1280, "conv_halo_kernel<256, 16", False, 0, None), (2, 64, 64, 640, "conv_halo_kernel<128, 64", False, 0, None),
+                                                        (14, 64, 64, 128, "gemm_big_kernel<256, 128", False, 0, None), (3, 8, 1280, 1280, "gemm_big_kernel<128, 160", True, 0, None),
+                                                        (2, 32, 320, 320, "", None, 0, 1e-2)]:
+        x, w, bias = rnd(Bn, Cin, H, H, seed=1), rnd(Cout, Cin, 3, 3, scale=0.02 if legacy else 0.05, seed=2), rnd(Cout, dtype=torch.float32, seed=3)
+        wk = w.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous()
+        d = _conv_desc(Bn, H, Cin, Cout)
+        d.bias = bias.data_ptr()
+        name, nsplit = kernel_name(d)
+        tag = f"conv {Bn}x{H}^2 {Cin}->{Cout} [{name[:28]}]"
+        X(f"{tag}: dispatch", name.startswith(kernel) and (split is None or (nsplit > 1) == split), f"{name!r} split {nsplit} tile {tile_of(d)}")
+        y, Ho, Wo = ops.conv3x3(_nhwc(x), wk, Bn, H, H, mode=mode, bias=bias)
+        ref, S = _conv_pair(x, w, bias, stride=2 if mode == 1 else 1)
+        B(tag, _nchw(y, Bn, Ho, Wo), ref, S, 9 * Cin + 1, 8 * 2e-3, legacy)
+        if "halo" in kernel:
+            res, rb = rnd(Bn * H * H, Cout, seed=4), rnd(Bn, Cout, seed=5)
+            y2, _, _ = ops.conv3x3(_nhwc(x), wk, Bn, H, H, bias=bias, residual=res, rowbias=rb)
+            B(f"{tag} epilogue", _nchw(y2, Bn, H, H), ref + rb.double()[:, :, None, None] + _nchw(res.double(), Bn, H, H),
+              S + rb.double().abs()[:, :, None, None] + _nchw(res.double().abs(), Bn, H, H), 9 * Cin + 3, 8 * 2e-3)
+            xb = torch.zeros_like(x)       # only the border pixels non-zero: every halo row / column of every tile must come back as exact zeros
+            xb[:, :, 0, :], xb[:, :, -1, :], xb[:, :, :, 0], xb[:, :, :, -1] = x[:, :, 0, :], x[:, :, -1, :], x[:, :, :, 0], x[:, :, :, -1]
+            yb, _, _ = ops.conv3x3(_nhwc(xb), wk, Bn, H, H)
+            refb, Sb = _conv_pair(xb, w)
+            B(f"{tag} border", _nchw(yb, Bn, H, H), refb, Sb, 9 * Cin, 8 * 2e-3)
+        del x, w, ref, S
+        torch.cuda.synchronize()
+    # Upsample2D = conv3x3(nearest-up2(x)) as four 2x2-tap phase problems, and its input gradient
+    for Bn, H, Cin, Cout in [(3, 40, 128, 512), (5, 16, 1280, 1280)]:
+        x, w, bias = rnd(Bn, Cin, H, H, seed=1), rnd(Cout, Cin, 3, 3, scale=0.03, seed=2), rnd(Cout, dtype=torch.float32, seed=3)
+        cv = layers.Conv3x3({"c.weight": w, "c.bias": bias}, "c", dev)
+        y, Ho, Wo = ops.conv_up2(_nhwc(x), cv, Bn, H, H)
+        ref, S = _conv_pair(x, w, bias, up=True)
+        # the phase weights are sums of up to four taps, rounded to bf16 once more (a second stored rounding): gate A and gate C, not gate B
+        C(f"conv_up2 phases {Bn}x{H}^2 {Cin}->{Cout}", _nchw(y, Bn, Ho, Wo), ref, 8 * 4e-3)
+        old, _, _ = ops.conv3x3(_nhwc(x), cv.wk, Bn, H, H, mode=ops.CONV_UP2, bias=cv.bias)
+        B(f"conv up2 3x3 gather {Bn}x{H}^2 {Cin}->{Cout}", _nchw(old, Bn, Ho, Wo), ref, S, 9 * Cin + 1, 8 * 2e-3)
+        g = rnd(Bn, Cout, Ho, Wo, seed=4)
+        xx = x.double().requires_grad_(True)
+        conv_ref(xx, w.double(), up=True).backward(g.double())
+        dx = ops.conv_up2_bwd(_nhwc(g), cv, Bn, H, H)
+        C(f"conv_up2 phases dgrad {Bn}x{H}^2 {Cin}->{Cout}", dx.view(Bn, H, H, Cin).permute(0, 3, 1, 2), xx.grad, 8 * 4e-3)
+        del x, w, ref, S, xx
+        torch.cuda.synchronize()
+
+
+# ============================================================================= attention
+def _attn_ref(q, k, v, H, kv_div=1):
+    Bq, T, Cc = q.shape
+    d = Cc // H
+    kk, vv = k.repeat_interleave(kv_div, 0), v.repeat_interleave(kv_div, 0)
+    sp = lambda t: t.reshape(t.shape[0], t.shape[1], H, d).permute(0, 2, 1, 3)
+    s = sp(q) @ sp(kk).transpose(-1, -2) * d ** -0.5
+    o = torch.softmax(s, -1) @ sp(vv)
+    return o.permute(0, 2, 1, 3).reshape(Bq, T, Cc), torch.logsumexp(s, -1)
+
+
+def _attn_case(Bq, H, Tq, Tk, d, kv_div, prescaled, legacy=False):
+    Cc, Bk = H * d, Bq // kv_div
+    tag = f"attn{' (pre-scaled q)' if prescaled else ''} B{Bq} H{H} Tq{Tq} Tk{Tk} d{d} kv_div{kv_div}"
+    seeds = (11, 12, 13, 14) if legacy else (1, 2, 3, 4)
+    q, k, v = rnd(Bq, Tq, Cc, seed=seeds[0]), rnd(Bk, Tk, Cc, seed=seeds[1]), rnd(Bk, Tk, Cc, seed=seeds[2])
+    fac = ops.q_prescale(d)
+    if prescaled:
+        X(f"{tag}: factor", fac is not None and abs(fac - d ** -0.5 * 1.4426950408889634) < 1e-12)
+        qp = (q.float() * fac).to(BF)                      # what the projection's epilogue writes (one rounding)
+        qr = (qp.double() / fac).requires_grad_(True)      # the query the stored values stand for
+    else:
+        qp, qr = q, q.double().requires_grad_(True)
+    kr, vr = k.double().requires_grad_(True), v.double().requires_grad_(True)
+    oref, lref = _attn_ref(qr, kr, vr, H, kv_div)
+    q2, k2, v2 = qp.reshape(Bq * Tq, Cc), k.reshape(Bk * Tk, Cc), v.reshape(Bk * Tk, Cc)
+    o, lse = ops.attn_fwd(q2, k2, v2, Bq, H, Tq, Tk, d, kv_div, need_lse=True, prescaled=prescaled)
+    C(f"{tag}: o", o.reshape(Bq, Tq, Cc), oref, 8 * 3e-3, legacy=2e-2 if legacy else None)
+    A(f"{tag}: lse", lse, lref, 8 * 1e-3)
+    o_b, lse_b = ops.attn_fwd(q2, k2, v2, Bq, H, Tq, Tk, d, kv_div, need_lse=True, prescaled=prescaled)
+    X(f"{tag}: forward reproducible", torch.equal(o, o_b) and torch.equal(lse, lse_b))
+    do = rnd(Bq, Tq, Cc, seed=seeds[3])
+    oref.backward(do.double())
+    leg = 3e-2 if legacy else None
+    if kv_div == 1:
+        dq, dk, dv = ops.attn_bwd(q2, k2, v2, o, do.reshape(Bq * Tq, Cc), lse, Bq, H, Tq, Tk, d, 1, prescaled=prescaled)
+        C(f"{tag}: dk", dk.reshape(Bk, Tk, Cc), kr.grad, 8 * 5e-3, legacy=leg)
+        C(f"{tag}: dv", dv.reshape(Bk, Tk, Cc), vr.grad, 8 * 5e-3, legacy=leg)
+    # the deterministic form of shared dK / dV: per-sample fp32 slabs + fixed-order sum (fd_sum_slabs), bit-identical between two launches
+    outs = []
+    for _ in range(2):
+        dko, dvo = torch.full((Bk * Tk, Cc), 7.0, dtype=torch.float32, device=dev), torch.full((Bk * Tk, Cc), -3.0, dtype=torch.float32, device=dev)
+        dq3, _, _ = ops.attn_bwd(q2, k2, v2, o, do.reshape(Bq * Tq, Cc), lse, Bq, H, Tq, Tk, d, kv_div, dk_out=dko, dv_out=dvo, prescaled=prescaled)
+        outs.append((dq3, dko, dvo))
+    X(f"{tag}: slab form reproducible", all(torch.equal(a, b) for a, b in zip(outs[0], outs[1])) and (kv_div > 1 or torch.equal(outs[0][0], dq)))
+    C(f"{tag}: dq", outs[0][0].reshape(Bq, Tq, Cc), qr.grad, 8 * 5e-3, legacy=leg)
+    A(f"{tag}: dk (slabs)", outs[0][1].reshape(Bk, Tk, Cc), kr.grad, 8 * 5e-3)
+    A(f"{tag}: dv (slabs)", outs[0][2].reshape(Bk, Tk, Cc), vr.grad, 8 * 5e-3)
+    if kv_div > 1:      # the atomics form
+        dk_acc = torch.zeros(Bk * Tk, Cc, dtype=torch.float32, device=dev)
+        dv_acc = torch.zeros_like(dk_acc)
+        _, dk, dv = ops.attn_bwd(q2, k2, v2, o, do.reshape(Bq * Tq, Cc), lse, Bq, H, Tq, Tk, d, kv_div, dk_acc=dk_acc, dv_acc=dv_acc, prescaled=prescaled)
+        A(f"{tag}: dk (atomics)", dk.reshape(Bk, Tk, Cc), kr.grad, 8 * 5e-3)
+        A(f"{tag}: dv (atomics)", dv.reshape(Bk, Tk, Cc), vr.grad, 8 * 5e-3)
+    torch.cuda.synchronize()
+
+
+def _small_attn_ref(q, k, v, key_valid, H, d, scale, causal):
+    """fp64 statement: softmax(q k^T * scale + mask) v, per (batch, head); masked entries of P are 0."""
+    Bq, T, _ = q.shape
+    sp = lambda t: t.double().view(Bq, T, H, d).permute(0, 2, 1, 3)
+    s = sp(q) @ sp(k).transpose(-1, -2) * scale
+    ok = torch.ones(Bq, 1, T, T, dtype=torch.bool, device=q.device)
+    if causal:
+        ok = ok & torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+    if key_valid is not None:
+        ok = ok & (key_valid != 0)[:, None, None, :]
+    P = torch.softmax(s.masked_fill(~ok, -math.inf), -1)
+    return P, (P @ sp(v)).permute(0, 2, 1, 3).reshape(Bq, T, H * d), ok
+
+
+def _small_attn():
+    for T in (1, 63, 64, 65, 77, 128):
+        for d in (32, 40, 64):
+            Bq, H = (2, 12) if (T, d) == (77, 64) else (1, 2)
+            Cc, scale = H * d, d ** -0.5
+            q, k, v, do = rnd(Bq, T, Cc, seed=1), rnd(Bq, T, Cc, seed=2), rnd(Bq, T, Cc, seed=3), rnd(Bq, T, Cc, seed=4)
+            g = torch.Generator().manual_seed(T * 1000 + d)
+            uncond = torch.zeros(Bq, T, dtype=torch.int32)
+            uncond[:, :2] = 1
+            rand = (torch.rand(Bq, T, generator=g) < 0.6).int()
+            rand[:, 0] = 1
+            worst = dict(P=0.0, o=0.0, dq=0.0, dk=0.0, dv=0.0)
+            ulps = dict(o=0.0, dq=0.0, dk=0.0, dv=0.0)
+            bwd_ok = (4 * T * (d + 1) + T * (T + 1)) * 4 <= 160 * 1024          # fd_small_attn_bwd: q, k, v, dO and dS tiles in LDS
+            zero = True
+            for causal in (True, False):
+                for kv in (None, uncond, rand):
+                    kvd = kv.to(dev) if kv is not None else None
+                    o, P = ops.small_attn_fwd(q, k, v, kvd, Bq, H, T, d, scale, causal=causal, save_p=True)
+                    Pr, orf, ok = _small_attn_ref(q, k, v, kvd, H, d, scale, causal)
+                    zero = zero and bool((P[~ok.expand_as(P)] == 0).all())
+                    for key, got, ref in (("P", P, Pr), ("o", o, orf)):
+                        worst[key] = max(worst[key], coarse(got, ref))
+                    ulps["o"] = max(ulps["o"], gate_c_stat(o, orf))
+                    if not bwd_ok:
+                        continue
+                    qr, kr, vr = (t.double().requires_grad_(True) for t in (q, k, v))
+                    _, oa, _ = _small_attn_ref(qr, kr, vr, kvd, H, d, scale, causal)
+                    oa.backward(do.double())
+                    dq, dk, dv = ops.small_attn_bwd(q, k, v, P, do, Bq, H, T, d, scale)
+                    for key, got, ref in (("dq", dq, qr.grad), ("dk", dk, kr.grad), ("dv", dv, vr.grad)):
+                        worst[key] = max(worst[key], coarse(got, ref))
+                        ulps[key] = max(ulps[key], gate_c_stat(got, ref))
+            tag = f"small attn B{Bq} H{H} T{T} d{d}"
+            X(f"{tag}: masked P exactly 0", zero)
+            print(f"[A {tag}] worst over causal x masks: " + "  ".join(f"{k_} {v_:.3e}" for k_, v_ in worst.items()) + "  (tol P 1e-5, o 1.6e-2, dq/dk/dv 2.4e-2)")
+            # P is fp32 and saved before any bf16 rounding: the fp16 test's band unchanged
+            X(f"{tag}: gate A", worst["P"] <= 1e-5 and worst["o"] <= 8 * 2e-3 and max(worst["dq"], worst["dk"], worst["dv"]) <= 8 * 3e-3, str(worst))
+            for key in ("o", "dq", "dk", "dv") if bwd_ok else ("o",):
+                Cv(f"{tag}: {key}", ulps[key])
+            if not bwd_ok:
+                try:
+                    ops.small_attn_bwd(q, k, v, P, do, Bq, H, T, d, scale)
+                    fail(f"{tag}: backward beyond its LDS not refused")
+                except RuntimeError as e:
+                    X(f"{tag}: backward refused for LDS", "LDS" in str(e), str(e))
+    Bq, H, T, d = 1, 2, 128, 128
+    q = rnd(Bq, T, H * d, seed=1)
+    o, P = ops.small_attn_fwd(q, q, q, None, Bq, H, T, d, d ** -0.5, causal=True, save_p=True)
+    Pr, orf, _ = _small_attn_ref(q, q, q, None, H, d, d ** -0.5, True)
+    A("small attn T128 d128: P", P, Pr, 1e-5)
+    C("small attn T128 d128: o", o, orf, 8 * 2e-3)
+    try:
+        ops.small_attn_bwd(q, q, q, P, q, Bq, H, T, d, d ** -0.5)
+        fail("small attn bwd (1, 2, 128, 128): not refused")
+    except RuntimeError as e:
+        X("small attn bwd (1, 2, 128, 128) refused for LDS", "LDS" in str(e), str(e))
+
+
+def _cross_block(Cc, Bq, HW, L, kv_div, r):
+    """fd_cross_attn_block: LayerNorm2 -> attn2.to_q -> attention over L prompt tokens -> attn2.to_out + residual -> LayerNorm3 in one launch, against fp64
+    and against the separate launches; with LoRA slabs of rank r and recording, every recorded output."""
+    H, d, M, Bk = 8, Cc // 8, Bq * HW, Bq // kv_div
+    tag = f"cross block C{Cc} B{Bq} HW{HW} L{L} kv_div{kv_div} r{r}"
+    x = rnd(M, Cc, seed=1)
+    g2, b2 = rnd(Cc, dtype=torch.float32, seed=2) * 0.2 + 1, rnd(Cc, dtype=torch.float32, seed=3) * 0.2
+    g3, b3 = rnd(Cc, dtype=torch.float32, seed=4) * 0.2 + 1, rnd(Cc, dtype=torch.float32, seed=5) * 0.2
+    wq, wo = rnd(Cc, Cc, scale=Cc ** -0.5, seed=6), rnd(Cc, Cc, scale=Cc ** -0.5, seed=7)
+    bo = rnd(Cc, dtype=torch.float32, seed=8) * 0.1
+    k, v = rnd(Bk * L, Cc, seed=9), rnd(Bk * L, Cc, seed=10)
+    vt = ops.transpose_btc(v, Bk, L, Cc, ops.CROSS_LP)
+    qs = ops.q_prescale(d)
+    xf = x.double()
+    n2 = F.layer_norm(xf, (Cc,), g2.double(), b2.double(), 1e-5)
+    if r == 0:
+        if not ops.cross_block_ok(M, Cc, H, L, HW):
+            return fail(f"{tag}: shape refused by cross_block_ok")
+        y, yn, st, _ = ops.cross_attn_block(x, (g2, b2, 1e-5), wq, k, vt, L, wo, bo, (g3, b3, 1e-5), H, HW, kv_div, need_stats=True)
+        q = n2 @ wq.double().t()
+        o, _ = _attn_ref(q.view(Bq, HW, Cc), k.double().view(Bk, L, Cc), v.double().view(Bk, L, Cc), H, kv_div)
+        yr = o.reshape(M, Cc) @ wo.double().t() + bo.double() + xf
+        C(f"{tag}: y", y, yr, 8 * 3e-3)
+        C(f"{tag}: LayerNorm3(y)", yn, F.layer_norm(yr, (Cc,), g3.double(), b3.double(), 1e-5), 8 * 4e-3)
+        A(f"{tag}: LayerNorm3 mean", st[:, 0], yr.mean(-1), 8 * 2e-3)
+        n2s = ops.layernorm(x, g2, b2, 1e-5)
+        q2 = ops.gemm(n2s, wq, colscale=(qs, Cc) if qs is not None else None)
+        o2 = ops.attn_fwd(q2, k, v, Bq, H, HW, L, d, kv_div, prescaled=qs is not None)
+        ys = ops.gemm(o2, wo, bias=bo, residual=x)
+        yns, _ = ops.layernorm(ys, g3, b3, 1e-5, save_stats=True)
+        A(f"{tag}: y vs the separate launches", y, ys, 8 * 2e-3)
+        A(f"{tag}: LayerNorm3(y) vs the separate launches", yn, yns, 8 * 3e-3)
+        y2, yn2, _, _ = ops.cross_attn_block(x, (g2, b2, 1e-5), wq, k, vt, L, wo, bo, (g3, b3, 1e-5), H, HW, kv_div)
+        return X(f"{tag}: reproducible", torch.equal(y, y2) and torch.equal(yn, yn2))
+    pairs = []
+    for seed in (11, 12):
+        p = layers.LoRAPair.__new__(layers.LoRAPair)
+        p.r, p.rp, p.K, p.N = r, (r + 7) // 8 * 8, Cc, Cc
+        p.down16 = torch.zeros(p.rp, Cc, dtype=BF, device=dev)
+        p.down16[:r] = rnd(r, Cc, scale=Cc ** -0.5, seed=seed)
+        p.up16 = torch.zeros(Cc, p.rp, dtype=BF, device=dev)
+        p.up16[:, :r] = rnd(Cc, r, scale=0.3, seed=seed + 10)
+        pairs.append(p)
+    lq, lo_ = pairs
+    if not ops.cross_block_ok(M, Cc, H, L, HW, lq.rp):
+        return fail(f"{tag}: shape refused by cross_block_ok")
+    y, yn, st, rec = ops.cross_attn_block(x, (g2, b2, 1e-5), wq, k, vt, L, wo, bo, (g3, b3, 1e-5), H, HW, kv_div, lora_q=lq, lora_o=lo_, record=True, q_prescaled=qs is not None)
+    y0, yn0, _, none = ops.cross_attn_block(x, (g2, b2, 1e-5), wq, k, vt, L, wo, bo, (g3, b3, 1e-5), H, HW, kv_div, lora_q=lq, lora_o=lo_)
+    X(f"{tag}: recording does not change the values", none is None and torch.equal(y, y0) and torch.equal(yn, yn0))
+    n2s, ln2s = ops.layernorm(x, g2, b2, 1e-5, save_stats=True)
+    tq = ops.gemm(n2s, lq.down16)
+    q2 = ops.gemm(n2s, wq, a2=tq, b2=lq.up16, colscale=(qs, Cc) if qs is not None else None)
+    o2, lse2 = ops.attn_fwd(q2, k, v, Bq, H, HW, L, d, kv_div, need_lse=True, prescaled=qs is not None)
+    to = ops.gemm(o2, lo_.down16)
+    ys = ops.gemm(o2, wo, a2=to, b2=lo_.up16, bias=bo, residual=x)
+    yns, ln3s = ops.layernorm(ys, g3, b3, 1e-5, save_stats=True)
+    for nm, got, ref, tol in (("LayerNorm2 statistics", rec["ln2"], ln2s, 8 * 1e-5), ("n2", rec["n2"], n2s, 8 * 1e-3), ("t_q", rec["tq2"], tq, 8 * 1e-3),
+                              ("q (as the backward takes it)", rec["q2"], q2, 8 * 2e-3), ("o", rec["o2"], o2, 8 * 3e-3), ("lse", rec["lse2"], lse2, 8 * 1e-3),
+                              ("t_o", rec["to2"], to, 8 * 3e-3), ("y", y, ys, 8 * 2e-3), ("LayerNorm3(y)", yn, yns, 8 * 3e-3), ("LayerNorm3 statistics", st, ln3s, 8 * 2e-3)):
+        A(f"{tag}: {nm} vs the separate launches", got, ref, tol)
+    q = n2 @ wq.double().t() + (n2 @ lq.down16.double().t()) @ lq.up16.double().t()
+    o, lse = _attn_ref(q.view(Bq, HW, Cc), k.double().view(Bk, L, Cc), v.double().view(Bk, L, Cc), H, kv_div)
+    o = o.reshape(M, Cc)
+    yr = o @ wo.double().t() + (o @ lo_.down16.double().t()) @ lo_.up16.double().t() + bo.double() + xf
+    C(f"{tag}: n2", rec["n2"], n2, 8 * 2e-3)
+    C(f"{tag}: y", y, yr, 8 * 4e-3)
+    C(f"{tag}: o", rec["o2"], o, 8 * 4e-3)
+    A(f"{tag}: lse", rec["lse2"], lse, 8 * 2e-3)
+    # the attention backward fed with what the fused forward recorded, against autograd of the fp64 statement
+    qf, kf, vf = q.detach().view(Bq, HW, Cc).requires_grad_(True), k.double().view(Bk, L, Cc).requires_grad_(True), v.double().view(Bk, L, Cc).requires_grad_(True)
+    oa, _ = _attn_ref(qf, kf, vf, H, kv_div)
+    do = rnd(M, Cc, seed=21)
+    oa.backward(do.double().view(Bq, HW, Cc))
+    dko, dvo = torch.empty(Bk * L, Cc, dtype=torch.float32, device=dev), torch.empty(Bk * L, Cc, dtype=torch.float32, device=dev)
+    dq, _, _ = ops.attn_bwd(rec["q2"], k, v, rec["o2"], do, rec["lse2"], Bq, H, HW, L, d, kv_div, dk_out=dko, dv_out=dvo, prescaled=qs is not None)
+    A(f"{tag}: dq from the fused recording", dq, qf.grad.reshape(M, Cc), 8 * 5e-3)
+    A(f"{tag}: dK from the fused recording", dko, kf.grad.reshape(Bk * L, Cc), 8 * 5e-3)
+    A(f"{tag}: dV from the fused recording", dvo, vf.grad.reshape(Bk * L, Cc), 8 * 5e-3)
+
+
+def attention():
+    _attn_case(2, 8, 1024, 1024, 40, 1, False, legacy=True)        # the attention check of the former kernels(), its seeds and bands
+    for Bq, H, Tq, Tk, d, kv_div in [(2, 8, 1024, 1024, 40, 1), (2, 8, 256, 256, 80, 1), (1, 4, 64, 64, 160, 1), (2, 4, 300, 77, 40, 1), (4, 8, 1024, 13, 40, 2)]:
+        if (Tq, Tk, d) != (1024, 1024, 40):
+            _attn_case(Bq, H, Tq, Tk, d, kv_div, False)
+        if d == 40:
+            _attn_case(Bq, H, Tq, Tk, d, kv_div, True)
+    # q, k, v as column slices of ONE [M, 3C] buffer, dq / dk / dv written as slices of one gradient buffer: bit-identical to the contiguous call
+    for Bq, H, T, d in [(1, 4, 64, 160), (2, 8, 256, 80)]:
+        Cc = H * d
+        qkv = rnd(Bq * T, 3 * Cc, seed=1)
+        q, k, v = qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:]
+        qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+        o_ref, lse_ref = ops.attn_fwd(qc, kc, vc, Bq, H, T, T, d, 1, need_lse=True)
+        o, lse = ops.attn_fwd(q, k, v, Bq, H, T, T, d, 1, need_lse=True)
+        do = rnd(Bq * T, Cc, seed=4)
+        dq_r, dk_r, dv_r = ops.attn_bwd(qc, kc, vc, o_ref, do, lse_ref, Bq, H, T, T, d, 1)
+        dqkv = torch.full((Bq * T, 3 * Cc), float("nan"), dtype=BF, device=dev)
+        dq, dk, dv = ops.attn_bwd(q, k, v, o, do, lse, Bq, H, T, T, d, 1, dqkv=dqkv)
+        X(f"attn strided qkv B{Bq} H{H} T{T} d{d}: bit-identical to the contiguous call",
+          torch.equal(o, o_ref) and torch.equal(lse, lse_ref) and dq.data_ptr() == dqkv.data_ptr() and bool(torch.isfinite(dqkv.float()).all()) and
+          torch.equal(dqkv[:, :Cc], dq_r) and torch.equal(dqkv[:, Cc:2 * Cc], dk_r) and torch.equal(dqkv[:, 2 * Cc:], dv_r))
+    # small upstream gradients: -D = -rowsum(dO o O) rides in three 16-bit pieces of the dO . V^T contraction (split3_scaled, whose smallest-normal
+    # threshold differs under FD_BF16); relative accuracy must not depend on the scale of dO
+    Bq, H, T, d = 2, 8, 1024, 40
+    Cc, fac = H * d, ops.q_prescale(d)
+    q, k, v = rnd(Bq, T, Cc, seed=1), rnd(Bq, T, Cc, seed=2), rnd(Bq, T, Cc, seed=3)
+    for prescaled in (False, True):
+        qp = (q.float() * fac).to(BF) if prescaled else q
+        q2, k2, v2 = qp.reshape(Bq * T, Cc), k.reshape(Bq * T, Cc), v.reshape(Bq * T, Cc)
+        o, lse = ops.attn_fwd(q2, k2, v2, Bq, H, T, T, d, 1, need_lse=True, prescaled=prescaled)
+        for gscale in (1.0, 1e-3, 1e-4):
+            qr = ((qp.double() / fac) if prescaled else q.double()).requires_grad_(True)
+            kr, vr = k.double().requires_grad_(True), v.double().requires_grad_(True)
+            oref, _ = _attn_ref(qr, kr, vr, H, 1)
+            do = (rnd(Bq, T, Cc, seed=4).float() * gscale).to(BF)
+            oref.backward(do.double())
+            dko, dvo = torch.empty(Bq * T, Cc, dtype=torch.float32, device=dev), torch.empty(Bq * T, Cc, dtype=torch.float32, device=dev)
+            dq, _, _ = ops.attn_bwd(q2, k2, v2, o, do.reshape(Bq * T, Cc), lse, Bq, H, T, T, d, 1, dk_out=dko, dv_out=dvo, prescaled=prescaled)
+            tag = f"attn bwd dO x {gscale}{' (pre-scaled q)' if prescaled else ''}"
+            # bf16 keeps fp32's exponent range: dq ~ 1e-5 is a normal number, so the fp16 test's subnormal-spacing allowance is not needed
+            A(f"{tag}: dq", dq.reshape(Bq, T, Cc), qr.grad, 8 * 5e-3)
+            A(f"{tag}: dk", dko.reshape(Bq, T, Cc), kr.grad, 8 * 5e-3)
+            A(f"{tag}: dv", dvo.reshape(Bq, T, Cc), vr.grad, 8 * 5e-3)
+    # pre-scaled-q forward whose first key tile lies ~200 below the others: the rescale factor must not overflow into NaN
+    Bq, H, T, d = 1, 4, 256, 40
+    Cc = H * d
+    q, k, v = rnd(Bq, T, Cc, seed=1).clone(), rnd(Bq, T, Cc, seed=2).clone(), rnd(Bq, T, Cc, seed=3)
+    qv, kv = q.view(Bq, T, H, d), k.view(Bq, T, H, d)
+    qv[..., 0] = 36.0
+    kv[..., 0] = 0.0
+    kv[:, :64, :, 0] = -36.0
+    qp = (q.float() * fac).to(BF)
+    oref, lref = _attn_ref(qp.double() / fac, k.double(), v.double(), H, 1)
+    o, lse = ops.attn_fwd(qp.reshape(Bq * T, Cc), k.reshape(Bq * T, Cc), v.reshape(Bq * T, Cc), Bq, H, T, T, d, 1, need_lse=True, prescaled=True)
+    X("attn fwd, first key tile far below the rest: finite", bool(torch.isfinite(o).all()) and bool(torch.isfinite(lse).all()))
+    C("attn fwd, first key tile far below the rest: o", o.reshape(Bq, T, Cc), oref, 8 * 3e-3)
+    A("attn fwd, first key tile far below the rest: lse", lse, lref, 8 * 1e-3)
+    # fd_attn_bwd_prep: D[b, h, t] = sum_c dO * O over the head's d columns, fp32: the fp16 test's band unchanged, and gate B1 with the fp32 half-ulp
+    for Bq, H, T, d in [(2, 12, 77, 64), (2, 8, 1024, 40)]:
+        o, do = rnd(Bq * T, H * d, seed=1), rnd(Bq * T, H * d, seed=2)
+        D = torch.full((Bq, H, T), float("nan"), dtype=torch.float32, device=dev)
+        ops._call("fd_attn_bwd_prep", ops._p(o), ops._p(do), ops._p(D), Bq, H, T, d, ops._stream())
+        prod = (o.double() * do.double()).view(Bq, T, H, d)
+        B(f"attn_bwd_prep B{Bq} H{H} T{T} d{d}", D, prod.sum(-1).permute(0, 2, 1), prod.abs().sum(-1).permute(0, 2, 1), d, 1e-5)
+    _small_attn()
+    _cross_block(320, 2, 64, 5, 1, 0)
+    _cross_block(320, 4, 1024, 77, 2, 0)
+    _cross_block(640, 2, 64, 80, 1, 0)
+    _cross_block(320, 2, 64, 5, 1, 4)
+    _cross_block(320, 4, 1024, 77, 2, 4)
+    _cross_block(640, 2, 64, 80, 1, 16)
+    _cross_block(320, 4, 1024, 77, 2, 16)
+
+
+# ============================================================================= norms and elementwise
+ACTS = [("silu", F.silu), ("relu", F.relu), ("hardswish", F.hardswish), ("hardsigmoid", F.hardsigmoid), ("quick_gelu", lambda t: t * torch.sigmoid(1.702 * t)),
+        ("gelu", F.gelu)]
+
+
+def _groupnorm_case(Bn, HW, C1, C2, silu, legacy=False):
+    G, eps = 32, 1e-5
+    tag = f"groupnorm B{Bn} HW{HW} C{C1}+{C2} silu={int(silu)}"
+    if legacy:
+        x1, x2, Cc = rnd(Bn * HW, C1, seed=7), None, C1
+        gamma, beta = torch.ones(Cc, device=dev), torch.zeros(Cc, device=dev)
+    else:
+        x1 = (rnd(Bn * HW, C1, seed=1).float() * 2 + 0.5).to(BF)
+        x2 = (rnd(Bn * HW, C2, seed=2).float() - 0.3).to(BF) if C2 else None
+        Cc = C1 + C2
+        gamma, beta = rnd(Cc, dtype=torch.float32, seed=3) * 0.2 + 1, rnd(Cc, dtype=torch.float32, seed=4) * 0.2
+    xc = (torch.cat([x1, x2], 1) if C2 else x1).double().reshape(Bn, HW, Cc).permute(0, 2, 1).requires_grad_(True)
+    ref = F.group_norm(xc, G, gamma.double(), beta.double(), eps)
+    ref = F.silu(ref) if silu else ref
+    y, st = ops.groupnorm(x1, x2, Bn, HW, G, eps, gamma, beta, silu)
+    C(f"{tag}: fwd", y.reshape(Bn, HW, Cc).permute(0, 2, 1), ref, 8 * 2e-3, legacy=2e-2 if legacy else None)
+    xg = xc.detach().reshape(Bn, G, -1)
+    sref = torch.stack([xg.mean(-1), (xg.var(-1, unbiased=False) + eps).rsqrt()], -1)
+    A(f"{tag}: mean / rstd (fp32 statistics, the fp16 band of the statistics unchanged)", st, sref, 2e-5)
+    dy = rnd(Bn * HW, Cc, seed=5)
+    ref.backward(dy.double().reshape(Bn, HW, Cc).permute(0, 2, 1))
+    add1 = rnd(Bn * HW, C1, seed=6)
+    dx1, dx2 = ops.groupnorm_bwd(x1, x2, dy, Bn, HW, G, st, gamma, beta, silu, add1=add1)
+    gref = xc.grad.permute(0, 2, 1).reshape(Bn * HW, Cc)
+    C(f"{tag}: bwd dx1", dx1, gref[:, :C1] + add1.double(), 8 * 3e-3)
+    if C2:
+        C(f"{tag}: bwd dx2", dx2, gref[:, C1:], 8 * 3e-3)
+
+
+def norm_elementwise():
+    for Bn, HW, C1, C2, silu in [(2, 256, 320, 0, True), (3, 64, 1280, 640, True), (2, 100, 640, 320, False)]:
+        _groupnorm_case(Bn, HW, C1, C2, silu)
+    _groupnorm_case(2, 1024, 320, 0, True, legacy=True)
+    # from producer statistics (fd_groupnorm_fwd_stats_p through ops.groupnorm, fd_groupnorm_fwd_stats by name)
+    Bn, HW, Cc, G, eps = 4, 4096, 320, 32, 1e-5
+    a, w = rnd(Bn * HW, 320, seed=1), rnd(Cc, 320, scale=0.1, seed=2)
+    x = ops.gemm(a, w, gn_stats=True)
+    if getattr(x, "gn_stats", None) is None:
+        fail("groupnorm from producer statistics: the producer left none")
+    else:
+        st1, rows1 = x.gn_stats
+        gamma, beta = rnd(Cc, dtype=torch.float32, seed=3) * 0.2 + 1, rnd(Cc, dtype=torch.float32, seed=4) * 0.2
+        y, mr = torch.empty_like(x), torch.empty((Bn, G, 2), dtype=torch.float32, device=dev)
+        ops._call("fd_groupnorm_fwd_stats", ops._p(x), Cc, None, 0, Bn, HW, G, eps, ops._p(gamma), ops._p(beta), 1, ops._p(y), ops._p(mr), ops._p(st1), rows1, None, 0, ops._stream())
+        ref = F.silu(F.group_norm(x.double().view(Bn, HW, Cc).permute(0, 2, 1), G, gamma.double(), beta.double(), eps))
+        C("groupnorm_fwd_stats B4 HW4096 C320", y.view(Bn, HW, Cc).permute(0, 2, 1), ref, 8 * 2e-3)
+        y2, st2 = ops.groupnorm(x, None, Bn, HW, G, eps, gamma, beta, True)
+        X("groupnorm_fwd_stats == ops.groupnorm on the same producer statistics", torch.equal(y, y2) and torch.equal(mr, st2))
+        y0, st0 = ops.groupnorm(x.clone(), None, Bn, HW, G, eps, gamma, beta, True)          # the clone carries no statistics: reduce + apply
+        A("mean / rstd from producer statistics vs the two-launch form", st2, st0, 2e-5)
+    # batch invariance and run-to-run bit equality
+    HW, C1, C2, G, Bn = 64, 1280, 1280, 32, 3
+    x1, x2 = (rnd(Bn * HW, C1, seed=1).float() * 2 + 0.5).to(BF), (rnd(Bn * HW, C2, seed=2).float() - 0.3).to(BF)
+    gamma, beta, dy = rnd(C1 + C2, dtype=torch.float32, seed=3) * 0.2 + 1, rnd(C1 + C2, dtype=torch.float32, seed=4) * 0.2, rnd(Bn * HW, C1 + C2, seed=5)
+    y, st = ops.groupnorm(x1, x2, Bn, HW, G, 1e-5, gamma, beta, True)
+    dx1, dx2 = ops.groupnorm_bwd(x1, x2, dy, Bn, HW, G, st, gamma, beta, True)
+    y2, st2 = ops.groupnorm(x1, x2, Bn, HW, G, 1e-5, gamma, beta, True)
+    ok = torch.equal(y, y2) and torch.equal(st, st2) and torch.equal(dx1, ops.groupnorm_bwd(x1, x2, dy, Bn, HW, G, st, gamma, beta, True)[0])
+    for b in range(Bn):
+        sl = slice(b * HW, (b + 1) * HW)
+        yb, stb = ops.groupnorm(x1[sl].contiguous(), x2[sl].contiguous(), 1, HW, G, 1e-5, gamma, beta, True)
+        d1, d2 = ops.groupnorm_bwd(x1[sl].contiguous(), x2[sl].contiguous(), dy[sl].contiguous(), 1, HW, G, stb, gamma, beta, True)
+        ok = ok and torch.equal(yb, y[sl]) and torch.equal(stb[0], st[b]) and torch.equal(d1, dx1[sl]) and torch.equal(d2, dx2[sl])
+    X("groupnorm (64, 1280, 1280): batch-invariant and reproducible", ok)
+    for M, Cc, legacy in [(333, 1280, False), (64, 768, False), (2048, 320, True)]:
+        if legacy:
+            x, gamma, beta = rnd(M, Cc, seed=7), torch.ones(Cc, device=dev), torch.zeros(Cc, device=dev)
+        else:
+            x = (rnd(M, Cc, seed=1).float() * 3 + 1).to(BF)
+            gamma, beta = rnd(Cc, dtype=torch.float32, seed=2) * 0.2 + 1, rnd(Cc, dtype=torch.float32, seed=3) * 0.2
+        xr = x.double().requires_grad_(True)
+        ref = F.layer_norm(xr, (Cc,), gamma.double(), beta.double(), 1e-5)
+        y, st = ops.layernorm(x, gamma, beta, 1e-5, save_stats=True)
+        C(f"layernorm {M}x{Cc}: fwd", y, ref, 8 * 2e-3, legacy=2e-2 if legacy else None)
+        dy, add = rnd(M, Cc, seed=4), rnd(M, Cc, seed=5)
+        ref.backward(dy.double())
+        C(f"layernorm {M}x{Cc}: bwd + add", ops.layernorm_bwd(x, dy, gamma, st, add=add), xr.grad + add.double(), 8 * 3e-3)
+    # row softmax at every width class, incl. rows whose scaled entries reach |x * scale| ~ 1e4
+    rows = 37
+    for cols in (1, 7, 255, 256, 257, 4095, 4096):
+        x = (rnd(rows, cols, seed=cols).float() * 4).to(BF)
+        x[:5] = (rnd(5, cols, seed=cols + 1).float() * 5e3).clamp(-6e4, 6e4).to(BF)
+        sf, sb = 0.0, 0.0
+        for scale in (0.125, 1.0):
+            xr = x.double().requires_grad_(True)
+            ref = torch.softmax(xr * scale, -1)
+            p = ops.softmax_rows(x, scale)
+            A(f"softmax cols={cols} scale={scale}", p, ref, 8 * 2e-3)
+            dp = rnd(rows, cols, seed=cols + 2)
+            # the backward's statement takes the probabilities the kernel is given (p as stored), so that its band is its own
+            pr = p.double()
+            gref = scale * pr * (dp.double() - (pr * dp.double()).sum(-1, keepdim=True))
+            ds = ops.softmax_rows_bwd(p, dp, scale)
+            ref.backward(dp.double())
+            A(f"softmax bwd cols={cols} scale={scale}", ds, xr.grad, 8 * 5e-3)
+            # gate C per row: probabilities of one row share its scale (floor = 2^-3 x the row's largest probability)
+            sf = max(sf, float(((p.double() - ref.detach()).abs() / ulp_bf16(torch.maximum(ref.detach(), 0.125 * ref.detach().amax(-1, keepdim=True)))).max()))
+            sb = max(sb, gate_c_stat(ds, gref))
+        Cv(f"softmax cols={cols}", sf)
+        Cv(f"softmax bwd cols={cols} (from the stored p)", sb)
+    Bq, H, T, cols = 3, 4, 9, 77
+    x = (rnd(Bq * H * T, cols, seed=1).float() * 3).to(BF)
+    g = torch.Generator().manual_seed(7)
+    mask = torch.randn(Bq * T, cols, generator=g) * 2
+    mask[torch.rand(Bq * T, cols, generator=g) < 0.3] = -math.inf
+    mask[:, 0] = 0.0
+    mask = mask.to(dev)
+    r_ = torch.arange(Bq * H * T, device=dev)
+    mrow = (r_ // (H * T)) * T + r_ % T
+    ref = torch.softmax(0.5 * x.double() + mask[mrow].double(), -1)
+    p = ops.softmax_rows(x, 0.5, mask=mask, mask_t=T, mask_ht=H * T)
+    C("softmax masked", p, ref, 8 * 2e-3)
+    X("softmax masked: masked entries exactly 0", bool((p[ref == 0] == 0).all()))
+    mask2 = mask.clone()
+    mask2[4] = -math.inf
+    y = ops.softmax_rows(x, 0.5, mask=mask2, mask_t=T, mask_ht=H * T)
+    full = mrow == 4
+    X("softmax: a fully masked row comes back NaN, no other row does", bool(torch.isnan(y[full]).all()) and not bool(torch.isnan(y[~full]).any()))
+    A("softmax masked (other rows)", y[~full], ref[~full], 8 * 2e-3)
+    # GEGLU
+    M, Fh = 300, 1280
+    proj = rnd(M, 2 * Fh, seed=1)
+    pr = proj.double().requires_grad_(True)
+    a_, g_ = pr.chunk(2, dim=-1)
+    ref = a_ * F.gelu(g_)
+    C("geglu fwd", ops.geglu(proj), ref, 8 * 2e-3)
+    dy = rnd(M, Fh, seed=2)
+    ref.backward(dy.double())
+    C("geglu bwd", ops.geglu_bwd(proj, dy), pr.grad, 8 * 3e-3)
+    wi = torch.stack([proj[:, :Fh], proj[:, Fh:]], dim=2).reshape(M, 2 * Fh).contiguous()
+    d_il = ops.geglu_bwd_interleaved(wi, dy)
+    C("geglu bwd interleaved", torch.cat([d_il[:, 0::2], d_il[:, 1::2]], 1), pr.grad, 8 * 3e-3)
+    # activations and add over a second grid pass plus the n % 8 tail, and on the tail alone
+    n = GRID * 8 + 8 * 1001 + 3
+    x, dy = (rnd(n, seed=3).float() * 3).to(BF), rnd(n, seed=4)
+    tail = slice(n - 11, n)
+    for act, fn in ACTS:
+        xr = x.double().requires_grad_(True)
+        r = fn(xr)
+        yv = ops.act_fwd(x, act)
+        C(f"act {act} n={n}", yv, r, 8 * 2e-3)
+        A(f"act {act} tail", yv[tail], r[tail], 8 * 2e-3)
+        r.backward(dy.double())
+        dx = ops.act_bwd(x, dy, act)
+        C(f"act_bwd {act} n={n}", dx, xr.grad, 8 * 3e-3)
+        A(f"act_bwd {act} tail", dx[tail], xr.grad[tail], 8 * 3e-3)
+        xs = x[n - 11:].clone()            # the tail alone: n = 11, block 0 only
+        C(f"act {act} n=11", ops.act_fwd(xs, act), r[tail], 8 * 2e-3)
+        C(f"act_bwd {act} n=11", ops.act_bwd(xs, dy[n - 11:].clone(), act), xr.grad[tail], 8 * 3e-3)
+        del xr, r
+    a, b = rnd(n, seed=5), rnd(n, seed=6)
+    yv, ref = ops.add(a, b, 0.5, -2.0), 0.5 * a.double() - 2 * b.double()
+    C("add", yv, ref, 8 * 2e-3)
+    A("add tail", yv[tail], ref[tail], 8 * 2e-3)
+    yv = ops.add(a, None, -1.5, 3.0)
+    C("add b=None", yv, -1.5 * a.double(), 8 * 2e-3)
+    A("add b=None tail", yv[tail], -1.5 * a[tail].double(), 8 * 2e-3)
+    C("add n=11", ops.add(a[n - 11:].clone(), b[n - 11:].clone(), 0.5, -2.0), ref[tail], 8 * 2e-3)
+    del a, b, x, dy, ref, yv
+    # data movement with arithmetic
+    x = rnd(3, 100, 320, seed=6)
+    yt = ops.transpose_btc(x.reshape(300, 320), 3, 100, 320)
+    X("transpose_btc: exact, pad columns 0", yt.shape == (3, 320, 104) and torch.equal(yt[:, :, :100], x.permute(0, 2, 1)) and float(yt[:, :, 100:].abs().max()) == 0)
+    x = rnd(2, 8, 8, 64, seed=7)
+    C("downsum2x2", ops.downsum2x2(x.reshape(-1, 64), 2, 4, 4, 64).reshape(2, 4, 4, 64), x.double().reshape(2, 4, 2, 4, 2, 64).sum(dim=(2, 4)), 8 * 2e-3)
+    src, dst = rnd(64, 48, seed=11), torch.zeros(64, 80, dtype=BF, device=dev)
+    ops.copy_cols(src, dst[:, 32:], 48)
+    X("copy_cols: exact, other columns untouched", torch.equal(dst[:, 32:], src) and float(dst[:, :32].abs().max()) == 0)
+    Bn = 2
+    pre = (rnd(Bn * 16, 4, seed=20).float() * 2).to(BF)
+    yv = ops.nhwc_to_nchw(pre, Bn, 16, 3, out_dtype=BF, lo=-1.0, hi=1.0)
+    bit_equal("nhwc_to_nchw clamp", yv, pre[:, :3].reshape(Bn, 16, 3).permute(0, 2, 1).clamp(-1, 1).contiguous().view(yv.shape))
+    dimg = rnd(Bn, 3, 16, dtype=torch.float32, seed=21)
+    pm = pre[:, :3].float().reshape(Bn, 16, 3).permute(0, 2, 1)
+    A("clamp_bwd", ops.clamp_bwd(pre, dimg, Bn, 16, 3), dimg * ((pm >= -1) & (pm <= 1)), 1e-6)
+
+
+# ============================================================================= bit-exact: the only or final rounding is the cast
+def _f32_bits(bits):
+    return torch.tensor([bits], dtype=torch.int32).view(torch.float32).item()
+
+
+def bitexact():
+    sub = 2.0 ** -133          # the smallest bf16 subnormal (9.2e-41)
+    special = [0.0, -0.0, 1e-42, -1e-42, 2.0 ** -135, -(2.0 ** -135), 1 + 2.0 ** -8, -(1 + 2.0 ** -8), 1 + 3 * 2.0 ** -8, -(1 + 3 * 2.0 ** -8),
+               3.3895313892515355e38, -3.3895313892515355e38, _f32_bits(0x7F7F8000), -_f32_bits(0x7F7F8000), math.inf, -math.inf, math.nan,
+               1.1754943508222875e-38, -1.1754943508222875e-38, 1e-40, -1e-40, sub, -sub, sub / 2, -sub / 2, 3 * sub / 2, -3 * sub / 2, 1.0, -2.5]
+    for n in (1000, 2 * GRID + 77):
+        x = rnd(n, dtype=torch.float32, seed=n % 1000) * 100
+        sp = torch.tensor(special, dtype=torch.float32, device=dev)
+        x[:len(sp)] = sp
+        x[-len(sp):] = sp
+        for scale in (1.0, 1024.0, 0.3):
+            bit_equal(f"to_f16 n={n} scale={scale}", ops.to_f16(x, scale), (x * scale).to(torch.bfloat16))
+        h = x.to(BF)
+        subs = torch.tensor([sub, -sub, 127 * sub, 2.0 ** -126, -0.0, 0.0, 3.3895313892515355e38], dtype=torch.float32, device=dev).to(BF)
+        h[:len(subs)] = subs
+        h[-len(subs):] = subs
+        for scale in (1.0, 1.0 / 1024, -3.0):
+            bit_equal(f"to_f32 n={n} scale={scale}", ops.to_f32(h, scale), h.float() * scale)
+    for npairs in (1, 17, 40):
+        for scale in (1.0, 0.25):
+            _lora_refresh(npairs, scale)
+    # pure data movement on random 16-bit patterns, incl. patterns that are NaN in fp16 but finite in bf16 (0x7E00) and bf16 subnormals; bf16 NaN /
+    # inf patterns (exponent 0xFF) are mapped to finite ones so that every element compares by its bits
+    def patterns(*shape, seed):
+        p = torch.randint(0, 65536, shape, generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
+        p = torch.where((p & 0x7F80) == 0x7F80, p & 0xBFFF, p)
+        p.view(-1)[:6] = torch.tensor([0x7E00, 0xFE00, 0x7C01, 0x0001, 0x8001, 0x8000], dtype=torch.int32)
+        return (p - 65536 * (p >= 32768).int()).to(torch.int16).to(dev).view(BF)
+    src = patterns(64, 48, seed=1)
+    dst = torch.zeros(64, 80, dtype=BF, device=dev)
+    ops.copy_cols(src, dst[:, 32:], 48)
+    bit_equal("copy_cols on 16-bit patterns", dst[:, 32:].contiguous(), src)
+    x = patterns(300, 320, seed=2)
+    yt = ops.transpose_btc(x, 3, 100, 320)
+    bit_equal("transpose_btc on 16-bit patterns", yt[:, :, :100].contiguous(), x.view(3, 100, 320).permute(0, 2, 1).contiguous())
+    X("transpose_btc: pad columns +0", bool((bits16(yt[:, :, 100:]) == 0).all()))
+    x = patterns(2 * 16, 4, seed=3)
+    yv = ops.nhwc_to_nchw(x, 2, 16, 3, out_dtype=BF)
+    bit_equal("nhwc_to_nchw without clamp on 16-bit patterns", yv, x[:, :3].reshape(2, 16, 3).permute(0, 2, 1).contiguous().view(yv.shape))
+    # fp32-only entry points: the bf16 library's copies are the same code
+    Bn, H, W = 8, 48, 80
+    rects = torch.tensor([[0, 0, 0, 0], [30, 10, 20, 40], [0, 0, W, H], [60, 30, W, H], [5, 7, 33, 19], [70, 0, W, 10], [0, 40, 10, H], [W - 1, H - 1, W, H]], dtype=torch.int32)
+    factors = torch.tensor([2.0, 3.0, 0.5, -1.25, 0.0, 1.0 / 3.0, 7.0, 1e-3], dtype=torch.float32)
+    dimg = rnd(Bn, 3, H, W, dtype=torch.float32, seed=1)
+    ys, xs = torch.arange(H)[:, None], torch.arange(W)[None, :]
+    mask = torch.stack([(xs >= r[0]) & (xs < r[2]) & (ys >= r[1]) & (ys < r[3]) for r in rects.tolist()])[:, None].to(dev)
+    bit_equal("rect_scale", ops.rect_scale(dimg.clone(), rects.to(dev), factors.to(dev)), dimg * torch.where(mask, factors.to(dev)[:, None, None, None], torch.ones((), device=dev)))
+    n, nslab = 1028, 3
+    x = rnd(nslab, n, dtype=torch.float32, seed=5) * torch.logspace(-3, 3, nslab, device=dev)[:, None]
+    out = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+    ops._call("fd_sum_slabs", ops._p(x), ops._p(out), nslab, n, ops._stream())
+    bit_equal("sum_slabs n=1028 nslab=3", out, (x[0] + x[1]) + x[2])
+    g = rnd(1000, dtype=torch.float32, seed=20)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    g0 = g.clone()
+    ops.grad_finite_scale(g, 0.5, flag)
+    bit_equal("grad_finite_scale", g, g0 * 0.5)
+    g[17] = float("inf")
+    f0 = int(flag.item())
+    ops.grad_finite_scale(g, 1.0, flag)
+    X("grad_finite_scale: flag", f0 == 0 and int(flag.item()) == 1)
+
+
+def _lora_refresh(npairs, scale):
+    """fd_lora_refresh_multi: down16 = down.to(bf16), up16 = (up * scale).to(bf16) and their transposes, rank padding exactly +0, sentinels intact."""
+    ranks, dims = (1, 4, 16, 50), ((320, 320), (768, 320), (320, 1280), (1280, 768))
+    shapes = {}
+    for i in range(npairs):
+        r = ranks[i % 4]
+        K, N = dims[(i // 4) % 4]
+        shapes[f"d{i}"], shapes[f"u{i}"] = (r, K), (N, r)
+    bank = layers.ParamBank(shapes, dev)
+    bank.flat.copy_((torch.randn(bank.numel, generator=torch.Generator().manual_seed(npairs)) * 0.3).to(dev))
+    pairs, bufs, SENT = [], [], -7.0
+    for i in range(npairs):
+        p = layers.LoRAPair(bank, f"d{i}", f"u{i}")
+        b = dict(d=torch.full((p.rp, p.K + 24), SENT, dtype=BF, device=dev), dT=torch.full((p.K, p.rp + 8), SENT, dtype=BF, device=dev),
+                 u=torch.full((p.N, p.rp + 8), SENT, dtype=BF, device=dev), uT=torch.full((p.rp, p.N + 16), SENT, dtype=BF, device=dev))
+        p.place(b["d"][:, :p.K], b["dT"][:, :p.rp], b["u"][:, :p.rp], b["uT"][:, :p.N])
+        pairs.append(p)
+        bufs.append(b)
+    layers.refresh_pairs(pairs, scale)
+    bad = []
+    for i, (p, b) in enumerate(zip(pairs, bufs)):
+        down, up = bank.view(p.dn), bank.view(p.un)
+        r, rp = p.r, p.rp
+        dh, uh = down.to(torch.bfloat16), (up * scale).to(torch.bfloat16)
+        for name, got, ref in (("down16", p.down16[:r], dh), ("downT16", p.downT16[:, :r], dh.t()), ("up16", p.up16[:, :r], uh), ("upT16", p.upT16[:r], uh.t())):
+            if not torch.equal(bits16(got), bits16(ref)):
+                bad.append(f"pair {i} {name}")
+        for name, pad in (("down16", p.down16[r:]), ("downT16", p.downT16[:, r:]), ("up16", p.up16[:, r:]), ("upT16", p.upT16[r:])):
+            if not bool((bits16(pad) == 0).all()):
+                bad.append(f"pair {i} {name} rank padding is not +0")
+        for name, extra in (("down16", b["d"][:, p.K:]), ("downT16", b["dT"][:, rp:]), ("up16", b["u"][:, rp:]), ("upT16", b["uT"][:, p.N:])):
+            if not bool((extra == SENT).all()):
+                bad.append(f"pair {i} {name} wrote past its row")
+    X(f"lora refresh {npairs} pairs scale={scale}: bit-exact, padding +0, sentinels intact", not bad, "; ".join(bad[:6]))
+
+
+# ============================================================================= small convolutions, classifier pieces, ViT / face ops, evaluator grids
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+DINO_MEAN, DINO_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def _patchify_ref(x, mean, std, P):
+    m = torch.tensor(mean, dtype=torch.float32, device=x.device).double()[None, :, None, None]
+    s = torch.tensor(std, dtype=torch.float32, device=x.device).double()[None, :, None, None]
+    u = F.unfold(((x + 1) / 2 - m) / s, kernel_size=P, stride=P)
+    return u.permute(0, 2, 1).reshape(-1, u.shape[1])
+
+
+def _crop_ref(im, bb, Hh, Ww, S):
+    l, r, bt, tp = max(bb[0], 0), min(bb[2], Ww), max(bb[1], 0), min(bb[3], Hh)
+    face = F.pad(im[:, bt:tp, l:r], [max(-bb[0], 0), max(bb[2] - Ww, 0), max(-bb[1], 0), max(bb[3] - Hh, 0)], value=-1.0)
+    return F.interpolate(face[None], size=[S, S], mode="bilinear", align_corners=False)[0]
+
+
+def small_classifier_eval():
+    Bn, H, Cin, Cout = 2, 16, 4, 64
+    x = rnd(Bn, Cin, H, H, dtype=torch.float32, seed=1)
+    w = rnd(Cout, Cin, 3, 3, dtype=torch.float32, scale=0.2, seed=2)
+    bias = rnd(Cout, dtype=torch.float32, seed=3)
+    wk = w.permute(2, 3, 1, 0).reshape(9 * Cin, Cout).contiguous()
+    for stride in (1, 2):
+        y, Ho, Wo = ops.conv_small_cin(x, wk, bias, Bn, H, H, Cin, Cout, 3, stride)
+        xr = x.double().requires_grad_(True)
+        ref = F.conv2d(xr, w.double(), bias.double(), stride=stride, padding=1)
+        C(f"small conv s{stride}", _nchw(y, Bn, Ho, Wo), ref, 8 * 2e-3)
+        g = rnd(*ref.shape, seed=4)
+        ref.backward(g.double())
+        C(f"small conv bwd s{stride}", ops.conv_small_cin_bwd(_nhwc(g), wk, Bn, H, H, Cin, Cout, 3, stride), xr.grad, 8 * 2e-3)
+    for (ci, co, hh, ww, st, act, nchw) in [(4, 320, 64, 64, 1, "none", True), (3, 16, 45, 37, 2, "hardswish", True), (4, 512, 18, 22, 1, "none", False)]:
+        xs = rnd(3, ci, hh, ww, seed=21)
+        ws = rnd(co, ci, 3, 3, dtype=torch.float32, scale=0.2, seed=22)
+        bs = rnd(co, dtype=torch.float32, seed=23)
+        wks = ws.permute(2, 3, 1, 0).reshape(9 * ci, co).contiguous()
+        ref = F.conv2d(xs.double(), ws.double(), bs.double(), stride=st, padding=1)
+        ref = F.hardswish(ref) if act == "hardswish" else ref
+        xin = xs if nchw else xs.permute(0, 2, 3, 1).contiguous()
+        y, Ho, Wo = ops.conv_small_cin(xin, wks, bs, 3, hh, ww, ci, co, 3, st, nchw=nchw, act=act)
+        C(f"small conv fast path {ci}->{co} {hh}x{ww} s{st} {act} {'nchw' if nchw else 'nhwc'}", _nchw(y, 3, Ho, Wo), ref, 8 * 2e-3)
+    w1 = rnd(4, 4, 1, 1, dtype=torch.float32, seed=5)
+    xh = x.to(BF)
+    y, _, _ = ops.conv_small_cin(xh, w1.permute(2, 3, 1, 0).reshape(4, 4).contiguous(), None, Bn, H, H, 4, 4, 1)
+    C("1x1 conv", _nchw(y, Bn, H, H), F.conv2d(xh.double(), w1.double()), 8 * 2e-3)
+    Cc = 72
+    for k, s in [(3, 1), (3, 2), (5, 1), (5, 2)]:
+        xd = rnd(Bn, Cc, 14, 14, seed=6)
+        wd = rnd(Cc, 1, k, k, dtype=torch.float32, scale=0.3, seed=7)
+        bd = rnd(Cc, dtype=torch.float32, seed=8)
+        xr = xd.double().requires_grad_(True)
+        ref = F.hardswish(F.conv2d(xr, wd.double(), bd.double(), stride=s, padding=(k - 1) // 2, groups=Cc))
+        wkk = wd.reshape(Cc, k * k).t().contiguous()
+        y, Ho, Wo = ops.dwconv(_nhwc(xd), wkk, bd, Bn, 14, 14, Cc, k, s, "hardswish")
+        C(f"dwconv k{k}s{s}", _nchw(y, Bn, Ho, Wo), ref, 8 * 2e-3)
+        lin = F.conv2d(xr, wd.double(), None, stride=s, padding=(k - 1) // 2, groups=Cc)
+        g = rnd(*lin.shape, seed=9)
+        lin.backward(g.double())
+        C(f"dwconv bwd k{k}s{s}", _nchw(ops.dwconv_bwd(_nhwc(g), wkk, Bn, 14, 14, Cc, k, s), Bn, 14, 14), xr.grad, 8 * 3e-3)
+    xa, s, dy = rnd(Bn, 49, 120, seed=10), rnd(Bn, 120, seed=11), rnd(Bn, 49, 120, seed=12)
+    C("avgpool", ops.avgpool_hw(xa.reshape(-1, 120), Bn, 49, 120), xa.double().mean(1), 8 * 2e-3)
+    C("scale_channels", ops.scale_channels(xa.reshape(-1, 120), s, Bn, 49, 120).reshape(Bn, 49, 120), xa.double() * s.double()[:, None], 8 * 2e-3)
+    dx, ds = ops.scale_channels_bwd(xa.reshape(-1, 120), s, dy.reshape(-1, 120), Bn, 49, 120)
+    C("scale_channels dx", dx.reshape(Bn, 49, 120), dy.double() * s.double()[:, None], 8 * 2e-3)
+    C("scale_channels ds", ds, (dy.double() * xa.double()).sum(1), 8 * 3e-3)
+    C("avgpool bwd", ops.avgpool_hw_bwd(s, Bn, 49, 120).reshape(Bn, 49, 120), (s.double() / 49)[:, None].expand(Bn, 49, 120), 8 * 2e-3)
+    # patchify: forward to one bf16 ulp, pad columns exactly 0; backward fp32 (the fp16 test's band unchanged)
+    for N, S, P, Kp, norm in [(2, 56, 14, 592, "clip"), (2, 64, 16, 776, "dino")]:
+        mean, std = (CLIP_MEAN, CLIP_STD) if norm == "clip" else (DINO_MEAN, DINO_STD)
+        x = (torch.rand(N, 3, S, S, generator=torch.Generator().manual_seed(S + P)) * 2 - 1).to(BF).to(dev)
+        K3 = 3 * P * P
+        out = ops.patchify(x, mean, std, P, Kp)
+        ref = _patchify_ref(x.double(), mean, std, P)
+        err = float(((out[:, :K3].double() - ref).abs() / ulp_bf16(ref)).max())
+        print(f"[patchify {N}x{S} P{P} Kp{Kp} {norm}] max err {err:.3f} bf16 ulp (gate 1.0)")
+        X(f"patchify {N}x{S} P{P} {norm}: one bf16 ulp, pad columns +0", out.shape == (N * (S // P) ** 2, Kp) and err <= 1.0 and
+          bool((out[:, K3:] == 0).all()) and not bool(torch.signbit(out[:, K3:]).any()), f"{err:.3f}")
+        dp = rnd(out.shape[0], Kp, seed=5)
+        xr = x.double().requires_grad_(True)
+        for scale in (1.0 / 1024, 0.37):
+            xr.grad = None
+            (_patchify_ref(xr, mean, std, P) * dp[:, :K3].double()).sum().mul(scale).backward()
+            A(f"patchify bwd {norm} scale={scale}", ops.patchify_bwd(dp, std, N, S, P, scale=scale), xr.grad, 1e-6)
+            acc = rnd(N, 3, S, S, dtype=torch.float32, seed=6)
+            A(f"patchify bwd accumulate {norm} scale={scale}", ops.patchify_bwd(dp, std, N, S, P, scale=scale, out=acc.clone()), acc.double() + xr.grad, 1e-6)
+    # crop + resize 512 -> 224 with boxes spilling over each edge, a box larger than the image and an 8 px box
+    Hh = Ww = 512
+    S = 224
+    boxes = torch.tensor([[-40, 100, 200, 340], [350, 200, 560, 410], [100, -30, 300, 170], [150, 400, 350, 600], [-100, -50, 600, 650], [250, 251, 258, 259]],
+                         dtype=torch.int32, device=dev)
+    Bn = boxes.shape[0]
+    img = (torch.rand(Bn, 3, Hh, Ww, generator=torch.Generator().manual_seed(11)) * 2 - 1).to(BF).to(dev)
+    chips = ops.crop_resize(img, boxes, -1.0, S)
+    g = rnd(Bn, 3, S, S, dtype=torch.float32, seed=14)
+    dimg = ops.crop_resize_bwd(g, boxes, Bn, Hh, Ww, S)
+    X("crop_resize bwd reproducible", torch.equal(dimg, ops.crop_resize_bwd(g, boxes, Bn, Hh, Ww, S)))
+    worst = 0.0
+    for i, bb in enumerate(boxes.tolist()):
+        im = img[i].double().requires_grad_(True)
+        ref = _crop_ref(im, bb, Hh, Ww, S)
+        A(f"crop_resize 512->224 box {bb}", chips[i], ref, 8 * 2e-3)
+        worst = max(worst, gate_c_stat(chips[i], ref))
+        ref.backward(g[i].double())
+        A(f"crop_resize bwd box {bb}", dimg[i], im.grad, 1e-4)
+    Cv("crop_resize 512->224 (six boxes)", worst)
+    # fd_crop_resize_u8_fwd writes working-dtype chips from uint8 images: 48x64 -> 28^2, boxes over each edge, larger than the image, 2 pixels wide, no face;
+    # and a box of exactly S x S pixels, where every output is one tap: u / 255 * 2 - 1 in fp32 rounded once, bit for bit, for all 256 byte values
+    Hh, Ww, S = 48, 64, 28
+    bl = [[8, 6, 50, 40], [-7, 5, 30, 42], [40, 4, 75, 39], [10, -9, 44, 25], [12, 20, 46, 60], [-10, -12, 80, 70], [30, 10, 32, 40], [-1, -1, -1, -1]]
+    u8 = torch.randint(0, 256, (len(bl), Hh, Ww, 3), generator=torch.Generator().manual_seed(21), dtype=torch.int64).to(torch.uint8).to(dev)
+    chips = ops.crop_resize_u8(u8, torch.tensor(bl, dtype=torch.int32, device=dev), -1.0, S)
+    xu = (u8.double() / 255 * 2 - 1).permute(0, 3, 1, 2)
+    worst = 0.0
+    for i, bb in enumerate(bl[:-1]):
+        ref = _crop_ref(xu[i], bb, Hh, Ww, S)
+        A(f"crop_resize_u8 48x64->28 box {bb}", chips[i], ref, 8 * 2e-3)
+        worst = max(worst, gate_c_stat(chips[i], ref))
+    Cv("crop_resize_u8 48x64->28 (seven boxes)", worst)
+    X("crop_resize_u8: the no-face box is a chip of the fill", chips.dtype == BF and bool((chips[-1] == -1).all()))
+    S = 16
+    u8 = torch.zeros((1, 24, 40, 3), dtype=torch.uint8)
+    vals = torch.arange(256, dtype=torch.uint8).view(16, 16)
+    u8[0, 4:20, 8:24, 0], u8[0, 4:20, 8:24, 1], u8[0, 4:20, 8:24, 2] = vals, vals.t(), vals.flip(0)
+    chips = ops.crop_resize_u8(u8.to(dev), torch.tensor([[8, 4, 24, 20]], dtype=torch.int32, device=dev), -1.0, S)
+    bit_equal("crop_resize_u8 at scale one", chips[0], (u8.float() / 255 * 2 - 1).permute(0, 3, 1, 2)[0, :, 4:20, 8:24].to(BF).to(dev).contiguous())
+    _warp_affine()
+    # fp32 by the ABI: gate A only, the fp16 test's band unchanged
+    n = 2 * 4 * 64
+    eps, lat, x0p = rnd(2 * n, dtype=torch.float32, seed=1), rnd(n, dtype=torch.float32, seed=2), rnd(n, dtype=torch.float32, seed=3)
+    x0o, l0 = torch.empty_like(lat), lat.clone()
+    ops.cfg_dpm_step(eps, 7.5, lat, x0p, x0o, 0.9, 0.43, 0.8, -0.3, 0.11)
+    e = eps[:n].double() + 7.5 * (eps[n:].double() - eps[:n].double())
+    x0 = (l0.double() - 0.43 * e) / 0.9
+    A("dpm x0", x0o, x0, 1e-5)
+    A("dpm lat", lat, 0.8 * l0.double() + 0.3 * x0 - 0.11 * (x0 - x0p.double()), 1e-5)
+    p = rnd(5000, dtype=torch.float32, seed=4)
+    pr = p.double().clone().requires_grad_(True)
+    opt = torch.optim.AdamW([pr], lr=5e-3, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8)
+    m, v, ema = torch.zeros_like(p), torch.zeros_like(p), p.clone()
+    for step in range(1, 4):
+        g = rnd(5000, dtype=torch.float32, seed=10 + step)
+        pr.grad = g.double()
+        opt.step()
+        ops.adamw_ema(p, g, m, v, ema, 5e-3, 0.9, 0.999, 1e-8, 1e-2, step, 0.25)
+    A("adamw", p, pr.detach(), 1e-5)
+    # LoRA weight gradients: fp32 outputs, fp32 accumulation: gate A at the fp16 band, gate B1 with the fp32 half-ulp
+    for M, N, R in [(777, 768, 16), (1000, 1280, 50)]:
+        RP = 8 if R <= 8 else 16 if R <= 16 else 32 if R <= 32 else 64
+        Xm = rnd(M, N, seed=1)
+        Tm = torch.zeros(M, RP, dtype=BF, device=dev)
+        Tm[:, :R] = rnd(M, R, seed=2)
+        G = torch.ones(N, R, dtype=torch.float32, device=dev)
+        ops.lora_wgrad(Xm, Tm, G, R, 1, R, scale=0.5)
+        B(f"lora wgrad [N,R] {M}x{N} r{R}", G, 1 + 0.5 * Xm.double().t() @ Tm[:, :R].double(), 1 + 0.5 * Xm.double().abs().t() @ Tm[:, :R].double().abs(), M + 2, 1e-3)
+        G2 = torch.zeros(R, N, dtype=torch.float32, device=dev)
+        ops.lora_wgrad(Xm, Tm, G2, 1, N, R)
+        B(f"lora wgrad [R,N] {M}x{N} r{R}", G2, Tm[:, :R].double().t() @ Xm.double(), Tm[:, :R].double().abs().t() @ Xm.double().abs(), M + 1, 1e-3)
+    for R in (4, 12):
+        RP = 8 if R <= 8 else 16
+        probs = []
+        for gi, (M, N, sl) in enumerate([(4096, 320, False), (4096, 320, True), (1000, 1280, False), (26, 768, False), (2048, 640, True)] * 2):
+            Xw = rnd(M, N * (3 if sl else 1), seed=10 + gi)
+            Xm = Xw[:, N:2 * N] if sl else Xw
+            Tm = torch.zeros(M, RP, dtype=BF, device=dev)
+            Tm[:, :R] = rnd(M, R, seed=50 + gi)
+            probs.append((Xm, Tm, gi % 2 == 1))
+        single, batched = [], []
+        for Xm, Tm, trans in probs:
+            shape = (R, Xm.shape[1]) if trans else (Xm.shape[1], R)
+            single.append(torch.ones(shape, dtype=torch.float32, device=dev))
+            batched.append(torch.ones(shape, dtype=torch.float32, device=dev))
+        for (Xm, Tm, trans), G in zip(probs, single):
+            ops.lora_wgrad(Xm, Tm, G, *((1, Xm.shape[1]) if trans else (R, 1)), R, scale=0.5)
+        with ops.wgrad_batch():
+            for (Xm, Tm, trans), G in zip(probs, batched):
+                ops.lora_wgrad(Xm, Tm, G, *((1, Xm.shape[1]) if trans else (R, 1)), R, scale=0.5)
+            queued = float(batched[0].sum()) == batched[0].numel()
+        X(f"wgrad batch R={R}: queued until the context closes", queued)
+        for i, ((Xm, Tm, trans), a, b) in enumerate(zip(probs, single, batched)):
+            xd, td = Xm.double(), Tm[:, :R].double()
+            ref = 0.5 * (td.t() @ xd if trans else xd.t() @ td) + 1
+            S = 0.5 * (td.abs().t() @ xd.abs() if trans else xd.abs().t() @ td.abs()) + 1
+            A(f"wgrad single R={R} [{i}]", a, ref, 1e-3)
+            B(f"wgrad batched R={R} [{i}]", b, ref, S, Xm.shape[0] + 2, 1e-3)
+    _ot_assign()
+    _eval_grids()
+
+
+def _warp_affine():
+    """fd_warp_affine_fwd / _bwd: 512^2 images to 112^2 aligned chips through rotated similarity transforms, against the oracle's image pipeline and its autograd."""
+    from finetune_fair_diffusion_amd.fairness import alignment_sampling_matrix
+    from oracle import nn_sfnet as OS
+    Bn, Hh, Ww, crop = 2, 512, 512, 112
+    imgs = (torch.rand(Bn, 3, Hh, Ww, generator=torch.Generator().manual_seed(5)) * 2 - 1).to(BF).float()      # the oracle's pipeline is fp32
+    rng = np.random.RandomState(3)
+
+    def face(size, angle, centre):
+        p = (OS.SRC_LANDMARKS - 56.0) / 112 * size
+        c, s = math.cos(angle), math.sin(angle)
+        return p @ np.array([[c, s], [-s, c]]) + np.array(centre) + rng.randn(5, 2) * 0.5
+
+    lms = [face(120, 0.3, (200, 220)), face(260, -0.6, (300, 330)), face(180, 1.2, (470, 60))]
+    src = [0, 0, 1]
+    idx = torch.tensor(src, dtype=torch.int32, device=dev)
+    x = imgs.clone().requires_grad_(True)
+    ref = torch.stack([OS.image_pipeline(x[src[i]], lms[i], crop) for i in range(len(lms))])
+    gw = torch.randn(ref.shape, generator=torch.Generator().manual_seed(6))
+    (ref * gw).sum().backward()
+    Am = torch.tensor(np.stack([alignment_sampling_matrix(l, Hh, Ww, crop) for l in lms]), dtype=torch.float32, device=dev)
+    chips = ops.warp_affine(imgs.to(BF).to(dev), idx, Am, crop)
+    C("warp_affine 512->112", chips, ref.detach().to(dev), 8 * 2e-3)
+    dimg = torch.zeros(Bn, 3, Hh, Ww, dtype=torch.float32, device=dev)
+    ops.warp_affine_bwd(gw.to(dev).contiguous(), idx, Am, dimg, crop)
+    A("warp_affine bwd 512->112", dimg, x.grad.to(dev), 1e-4)
+    d2 = torch.zeros_like(dimg)
+    ops.warp_affine_bwd(gw.to(dev).contiguous(), idx, Am, d2, crop)
+    X("warp_affine bwd reproducible", torch.equal(dimg, d2))
+
+
+def _ot_assign():
+    from scipy.optimize import linear_sum_assignment
+    for N, K, S in [(5, 8, 20), (130, 16, 12)]:
+        rng = np.random.default_rng(1000 * N + K)
+        for degenerate in (False, True):
+            M = np.full((N, K), 0.75) if degenerate else np.sqrt(rng.random((N, K)) * 2.0)
+            counts = np.stack([np.bincount(rng.integers(0, K, N), minlength=K) for _ in range(S)]).astype(np.int32)
+            plan, seats = ops.ot_assign_sum(torch.from_numpy(M).to(dev), torch.from_numpy(counts).to(dev), seats=True)
+            torch.cuda.synchronize()
+            plan, seats = plan.cpu().numpy(), seats.cpu().numpy()
+            ref, onehot, ok = np.zeros((N, K)), np.zeros((N, K)), True
+            for s in range(S):
+                cols = np.repeat(np.arange(K), counts[s])
+                r, c = linear_sum_assignment(M[:, cols])
+                opt, got = M[r, cols[c]].sum(), M[np.arange(N), seats[s]].sum()
+                ok = ok and (np.bincount(seats[s], minlength=K) == counts[s]).all() and abs(got - opt) <= 1e-12 * max(1.0, abs(opt))
+                ref[r, cols[c]] += 1.0
+                onehot[np.arange(N), seats[s]] += 1.0
+            ok = ok and (plan == onehot).all() and plan.sum() == N * S and (degenerate or (plan == ref).all())
+            X(f"ot_assign N{N} K{K} S{S} degenerate={int(degenerate)}: feasible, optimal, equal to the host solver", bool(ok))
+
+
+def _eval_grids():
+    """fd_eval_grid_u8 and fd_eval_grid_attrs take a working-dtype image: uint8-exact against the host statements on the bf16 images."""
+    from finetune_fair_diffusion_amd import evaluate_images as EI, evaluation as E
+    i32 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.int32).to(dev).contiguous()
+    g = np.load(os.path.join(HERE, "golden", "reference_eval_grid.npz"))
+    for case in "ab":
+        im, bx, pr, mp = (g[f"{case}_{n}"] for n in ("images", "boxes", "preds", "maxprob"))
+        N, _, H, W = im.shape
+        order = E.grid_order(pr, mp, 2)
+        imgs = torch.from_numpy(im).to(BF)
+        ref = E.grid_host(imgs, order, bx, pr, mp, E.PALETTE_GENDER)
+        rows, cols, shape = E.grid_shape(N, H, W)
+        nbytes = shape[0] * shape[1] * shape[2]
+        buf = torch.full((nbytes + 64,), 0xA5, dtype=torch.uint8, device=dev)
+        out = ops.eval_grid(imgs.to(dev).contiguous(), i32(order), i32(bx), i32(pr), torch.as_tensor(np.asarray(mp), dtype=torch.float32).to(dev),
+                            torch.tensor(E.PALETTE_GENDER, dtype=torch.uint8, device=dev), out=buf[:nbytes].view(shape))
+        got = out.cpu().numpy()
+        X(f"eval_grid golden {case} ({H}x{W}): uint8-exact, nothing written behind", got.shape == ref.shape and bool((got == ref).all()) and bool((buf[nbytes:] == 0xA5).all()))
+    N, H, W = 7, 40, 37
+    rng = np.random.RandomState(71 + N)
+    images = torch.from_numpy(rng.uniform(-1, 1, (N, 3, H, W)).astype(np.float32)).clamp(-1, 1)
+    images[0, :, :2] = 1.0
+    images[0, :, 2:4] = -1.0
+    boxes = np.array([[0, 0, W - 1, H - 1], [-5, 10, 20, 50], [10, 10, 12, 30], [5, 5, 30, 30], [-1, -1, -1, -1], [20, 2, 35, 9], [3, 30, 33, 38]])
+    for n_attr in (1, 2, 3):
+        preds = np.stack([rng.randint(0, 2, N), rng.randint(0, 4, N), rng.randint(0, 2, N)])[:n_attr]
+        bars = rng.randint(1, H - 1, (n_attr, N))
+        bars[:, 0], bars[:, 1], bars[-1, 1] = -1, 0, H + 100
+        preds[:, 4], bars[:, 4] = -1, 1024
+        order = rng.permutation(N)
+        pal = EI.PALETTES[:n_attr]
+        imgs = images.to(BF)
+        ref = E.grid_attrs_img_host(imgs, order, boxes, preds, bars, pal)
+        rows, cols, shape = E.grid_attrs_shape(N, H, W, n_attr)
+        nbytes = shape[0] * shape[1] * shape[2]
+        PAD = 4096
+        buf = torch.full((PAD + nbytes + PAD,), 0xAB, dtype=torch.uint8, device=dev)
+        Pm = max(len(p) for p in pal)
+        pal_t = torch.tensor([p + [(255, 255, 255)] * (Pm - len(p)) for p in pal], dtype=torch.uint8, device=dev)
+        out = ops.eval_grid_attrs_img(imgs.to(dev).contiguous(), i32(order), i32(boxes), i32(preds), i32(bars), pal_t, out=buf[PAD:PAD + nbytes].view(shape))
+        got = out.cpu().numpy()
+        X(f"eval_grid_attrs N{N} {H}x{W} strips {n_attr}: uint8-exact, nothing written around",
+          got.shape == ref.shape and bool((got == ref).all()) and bool((buf[:PAD] == 0xAB).all()) and bool((buf[PAD + nbytes:] == 0xAB).all()))
+
+
+GROUPS = dict(gemm=gemm, conv=conv, attention=attention, norm_elementwise=norm_elementwise, bitexact=bitexact, small_classifier_eval=small_classifier_eval)
+
+if __name__ == "__main__":
+    which = sys.argv[1:] or list(GROUPS)
+    assert all(w in GROUPS for w in which), f"groups: {list(GROUPS)}"
+    _init()
+    for name in which:
+        del FAILS[:]
+        GROUPS[name]()
+        torch.cuda.synchronize()
+        if FAILS:
+            print(f"BF16 KERNEL CHECKS FAILED {name}: {len(FAILS)} failures")
+            for f_ in FAILS:
+                print("  -", f_)
+            sys.exit(1)
+        print(f"BF16 KERNEL CHECKS PASSED {name}")

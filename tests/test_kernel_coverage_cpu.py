@@ -25,6 +25,16 @@ ELSEWHERE = {
     "fd_ot_expected_targets": ("test_exp6_gpu.py", "test_expected_targets_kernel_matches_host"),
 }
 WRAPPER_MODULES = ("ops", "layers")
+# The bf16 library (same sources, -DFD_BF16) is checked kernel by kernel by tests/run_bf16_kernel_checks.py.  Entry points with no working-dtype operand
+# -- no ``void*`` parameter but ``stream`` -- compile to the same code in both libraries and may be listed here instead, each with its reason.
+BF16_SCRIPT = "run_bf16_kernel_checks.py"
+BF16_LAUNCHER = "test_kernels_bf16_gpu.py"
+BF16_SAME_CODE = {
+    "fd_eval_tally": "fp32 probabilities to integer counts",
+    "fd_eval_grid_attrs_u8": "uint8 images to a uint8 grid",
+    "fd_eval_grid_labels_u8": "paints uint8 glyph masks into a uint8 grid",
+    "fd_ot_expected_targets": "fp64 costs, integer counts, fp32 weights",
+}
 
 
 def _launches(fn):
@@ -106,6 +116,49 @@ def uncovered():
             continue
         missing[name] = sorted(f"{m}.{w}" for m, w in wr.get(name, ()))
     return missing
+
+
+def uncovered_bf16():
+    protos = lib.parse_header()
+    wr = wrappers()
+    calls, literals = exercised(os.path.join(ROOT, "tests", BF16_SCRIPT))
+    return {name: sorted(f"{m}.{w}" for m, w in wr.get(name, ())) for name in protos
+            if not (name in EXEMPT or name in literals or (wr.get(name, set()) & calls) or name in BF16_SAME_CODE)}
+
+
+def _prototype_text(name):
+    import re
+    text = open(os.path.join(ROOT, "include", "fairdiff_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    m = re.search(r"\b" + name + r"\s*\(([^;{]*)\)\s*;", text)
+    assert m, f"{name}: no prototype in include/fairdiff_hip.h"
+    return m.group(1)
+
+
+def test_every_launching_entry_point_has_a_bf16_kernel_check():
+    missing = uncovered_bf16()
+    lines = [f"  {n}  (wrappers: {', '.join(w) or 'none in ops.py / layers.py'})" for n, w in sorted(missing.items())]
+    assert not missing, (f"C-ABI entry points that tests/{BF16_SCRIPT} does not exercise on the bf16 library (call the wrapper or name the entry point there, "
+                         "or list it in BF16_SAME_CODE if it has no working-dtype operand):\n" + "\n".join(lines))
+
+
+def test_bf16_same_code_entries_have_no_working_dtype_operand():
+    import re
+    protos = lib.parse_header()
+    for name, reason in BF16_SAME_CODE.items():
+        assert name in protos and reason, name
+        params = [p.strip() for p in _prototype_text(name).split(",")]
+        untyped = [p for p in params if re.search(r"\bvoid\s*\*", p) and not re.search(r"\bstream$", p)]
+        assert not untyped, f"{name} takes {untyped}: an untyped operand may be a working-dtype buffer, so it needs a bf16 check of its own"
+    # the rule itself: an entry point that takes a working-dtype image may not be listed
+    assert any(re.search(r"\bvoid\s*\*", p) and not p.strip().endswith("stream") for p in _prototype_text("fd_eval_grid_u8").split(","))
+
+
+def test_bf16_launcher_adds_nothing_to_the_fp16_guard():
+    """tests/test_kernels_bf16_gpu.py matches the fp16 guard's glob: it must name no entry point and call no wrapper, so that it cannot satisfy that guard."""
+    calls, literals = exercised(os.path.join(ROOT, "tests", BF16_LAUNCHER))
+    assert not calls and not literals, (calls, literals)
 
 
 def test_exempt_host_queries_are_still_in_the_header():
