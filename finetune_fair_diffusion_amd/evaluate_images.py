@@ -20,6 +20,18 @@ the bytes with the reference's four fp32 roundings (``ops.eval_grid_attrs``).  A
 the others, as in the reference (:392, :643-645); only its indicator marks it.  The reference's aligned 112x112 chips are computed there but never
 saved: they are not built.  ``grid_attrs_host`` / ``grid_attrs_order`` are the plain host statements the grid kernel and the device ordering are
 tested against (tests/golden/reference_evalimages_grid.npz holds the reference's own arrays).
+
+``--original_imgs_dir DIR`` (build addition) names a second tree of the same layout, written by ``generate.py`` from the same prompts file and seed
+without the LoRA files, so that ``prompt_{i}/img_{j}.jpg`` of both trees were drawn from the same noise.  Each pair is then compared the way training
+regularises it: ``sim = <normalize(e_gen), normalize(e_ori)>`` of the CLIP ViT-H/14 and the DINOv2 ViT-B/14 embeddings of the ``Resize(224)`` images,
+``1 - loss_CLIP`` / ``1 - loss_DINO`` of exp-1-debias-gender/1-main-debias.py:1139-1175, :1860-1862, :1905-1910.  It adds
+
+  * ``semantics.pkl`` -- ``[sim_clip_all, sim_dino_all]``, each a dict from prompt index to a CPU float32 tensor [N] in image order;
+  * ``semantics.json`` -- per prompt the mean, the minimum and the image number of the least preserved pair, and the mean over prompts
+    (``semantics_summary``);
+
+and leaves the three files above exactly as they are without it.  The encoders' weights come from ``FD_CLIP_VISION_DIR`` / ``FD_DINO_WEIGHTS`` as in
+training (``--synthetic``: ``synthetic_vit_state``).
 """
 import argparse
 import glob
@@ -32,6 +44,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from .evaluation import (LABEL_FONT_SIZE, PALETTE_GENDER, PALETTE_RACE, IndexLabels, _json_safe, draw_labels, gap_metrics, grid_attrs_shape,  # noqa: F401
                          paint_attrs_tiles)
@@ -42,6 +55,8 @@ ATTR_K = (2, 4, 2)                   # gender, race, age: classes of the three t
 TABLE_ATTRS = [(0, 2), (2, 4), (6, 2)]
 DECODE_THREADS = 8                   # fixed: the pool only hides JPEG decoding behind the device work, it is not sized by the machine
 SYNTHETIC_SEEDS = (9101, 9102, 9103)
+SYNTHETIC_VIT_SEEDS = (21, 22)       # CLIP, DINOv2
+VIT_KEYS = ("clip_vision", "dino")
 
 
 def parse_args(input_args=None):
@@ -65,11 +80,14 @@ def parse_args(input_args=None):
     a("--face_provider", type=str, default="synthetic", help="(build addition) 'synthetic' or 'detector', as in train.py")
     a("--grid", type=str, default="gender_race", choices=["gender_race", "gender_race_age", "off"],
       help="(build addition) which of the reference's two grids to paint; its main runs gender_race")
-    # the two flags below are absent from the namespace unless given (argparse.SUPPRESS): without them the arguments are the reference's plus --grid etc.
+    # the three flags below are absent from the namespace unless given (argparse.SUPPRESS): without them the arguments are the reference's plus --grid etc.
     a("--index_font", type=str, default=argparse.SUPPRESS,
       help="(build addition) PATH of a TrueType font file, or 'default' for Pillow's embedded one: print each image's index on its tile as the reference "
            "does with Arial Bold; not given: no index text")
     a("--index_font_size", type=int, default=argparse.SUPPRESS, help=f"(build addition) point size of --index_font; default {LABEL_FONT_SIZE}, the reference's")
+    a("--original_imgs_dir", type=str, default=argparse.SUPPRESS,
+      help="(build addition) a tree laid out like --generated_imgs_dir, generated from the same prompts and seed without the LoRA files: adds the CLIP / "
+           "DINOv2 cosine similarity of every image pair (semantics.pkl, semantics.json); not given: no such files")
     return p.parse_args(input_args) if input_args is not None else p.parse_args()
 
 
@@ -163,8 +181,122 @@ def synthetic_classifier_state(which):
     return {k: (v.half().float() if v.is_floating_point() else v) for k, v in sd.items()}
 
 
+def _default_cfgs(cfgs):
+    from .factory import SD15, TINY
+    return cfgs or (TINY if os.environ.get("FD_TINY") else SD15)
+
+
+def synthetic_vit_state(which, cfgs=None):
+    """``--synthetic --original_imgs_dir``: seeded random weights of image encoder ``which`` (0 CLIP, 1 DINOv2) at the size ``cfgs`` gives it
+    (default: as in ``main``), representable in fp16."""
+    from . import weights as W
+    sd = W.synthetic_state_dict(W.vit_param_shapes(_default_cfgs(cfgs)[VIT_KEYS[which]]), seed=SYNTHETIC_VIT_SEEDS[which])
+    return {k: (v.half().float() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
 def _numbered(paths, number):
     return sorted(paths, key=number)
+
+
+def _prompt_number(folder):
+    return int(folder.split("_")[-1])
+
+
+def _image_number(path):
+    return int(path.split("_")[-1].split(".")[0])
+
+
+def _prompt_folders(root):
+    return _numbered(glob.glob(os.path.join(root, "prompt_*")), _prompt_number)
+
+
+def _image_paths(folder):
+    return _numbered(glob.glob(os.path.join(folder, "img_*.jpg")), _image_number)
+
+
+# ------------------------------------------------------------------------------------------ semantics preservation (--original_imgs_dir)
+def pair_paths(generated_dir, original_dir):
+    """{prompt index: [(generated path, original path), ...]} in the evaluator's numeric order: every ``prompt_i/img_j.jpg`` of the generated tree
+    with the file at the same relative path of the original tree.  A generated image without its counterpart is refused; what the original tree
+    holds beyond that is ignored."""
+    pairs, missing = {}, []
+    for folder in _prompt_folders(generated_dir):
+        paths = _image_paths(folder)
+        if not paths:
+            continue
+        ori = [os.path.join(original_dir, os.path.relpath(p, generated_dir)) for p in paths]
+        missing += [o for o in ori if not os.path.isfile(o)]
+        pairs[_prompt_number(folder)] = list(zip(paths, ori))
+    if missing:
+        raise ValueError(f"--original_imgs_dir: {missing[0]} is missing ({len(missing)} of the generated tree's images have no counterpart at the same "
+                         "relative path; both trees must come from the same prompts file and seed)")
+    return pairs
+
+
+def semantics_summary(sims_by_prompt, image_numbers_by_prompt):
+    """The content of ``semantics.json`` from the content of ``semantics.pkl``: ``sims_by_prompt`` = [sim_clip_all, sim_dino_all] ({prompt index:
+    [N] similarities in image order}), ``image_numbers_by_prompt`` = {prompt index: the N numbers ``j`` of ``img_j.jpg``}.  ``argmin_*`` is the image
+    NUMBER of the least preserved pair (the first one on a tie); ``mean`` is the mean over prompts of the per-prompt means, as in ``metrics.json``."""
+    per = {}
+    for i, numbers in image_numbers_by_prompt.items():
+        row = {}
+        for name, sims in zip(("CLIP", "DINO"), sims_by_prompt):
+            s = np.asarray(sims[i], dtype=np.float64).reshape(-1)
+            assert len(s) == len(numbers) and len(s) > 0, (i, name, len(s), len(numbers))
+            row["sim_" + name], row["min_sim_" + name], row["argmin_" + name] = float(s.mean()), float(s.min()), int(numbers[int(s.argmin())])
+        per[str(i)] = {f"{k}_{name}": row[f"{k}_{name}"] for k in ("sim", "min_sim", "argmin") for name in ("CLIP", "DINO")}
+        per[str(i)]["pairs"] = len(numbers)
+    mean = {k: float(np.array([m[k] for m in per.values()]).mean()) for k in (("sim_CLIP", "sim_DINO") if per else ())}
+    return _json_safe({"per_prompt": per, "mean": mean})
+
+
+def _resize_full(u8, S):
+    """``transforms.Resize(S)`` of whole decoded images [n,H,W,3] uint8 -> [n,3,S,S] working dtype: the crop kernel on the full-image box, what
+    ``FairnessTrainer.resize_small`` does to training's images."""
+    from . import ops
+    n, H, W, _ = u8.shape
+    box = torch.tensor([[0, 0, W, H]] * n, dtype=torch.int32, device=u8.device)
+    return ops.crop_resize_u8(u8, box, -1.0, S)
+
+
+def embedding_similarity(e_gen, e_ori):
+    """``<normalize(e_gen), normalize(e_ori)>`` per row in fp32: one minus the ``loss`` of ``vit.feature_loss_and_grad(e_gen, normalize(e_ori), w)``."""
+    return (F.normalize(e_gen.float(), dim=-1) * F.normalize(e_ori.float(), dim=-1)).sum(-1)
+
+
+def pair_similarity(clip, dino, u8_gen, u8_ori):
+    """``1 - loss_CLIP`` and ``1 - loss_DINO`` of the training step (:1905-1910) for n pairs of decoded images: u8_gen [n,H,W,3], u8_ori [n,H',W',3]
+    uint8 on the device, ``clip`` / ``dino`` the two ``vit.VisionTransformer`` -> (sim_clip [n], sim_dino [n]) fp32 on the device.  Images of one
+    size go through each encoder as one batch of 2n; an encoder input size is resized once."""
+    n = u8_gen.shape[0]
+    assert u8_ori.shape[0] == n and n >= 1, (u8_gen.shape, u8_ori.shape)
+    groups = [torch.cat([u8_gen, u8_ori])] if u8_gen.shape == u8_ori.shape else [u8_gen, u8_ori]
+    chips, sims = {}, []
+    for enc in (clip, dino):
+        S = enc.config.image_size
+        if S not in chips:
+            chips[S] = [_resize_full(u, S) for u in groups]
+        e = torch.cat([enc.forward(c) for c in chips[S]])
+        sims.append(embedding_similarity(e[:n], e[n:]))
+    return sims[0], sims[1]
+
+
+def _load_encoders(args, cfgs, device):
+    from . import weights as W
+    from .vit import VisionTransformer
+    if args.synthetic:
+        sds = [synthetic_vit_state(k, cfgs) for k in range(2)]
+    else:
+        from .pretrained import load_clip_vision, load_dino
+        sds = [load_clip_vision(os.environ["FD_CLIP_VISION_DIR"], cfgs["clip_vision"]), load_dino(os.environ["FD_DINO_WEIGHTS"], cfgs["dino"])]
+    return (VisionTransformer(cfgs["clip_vision"], sds[0], device, W.CLIP_IMAGE_MEAN, W.CLIP_IMAGE_STD),
+            VisionTransformer(cfgs["dino"], sds[1], device, W.DINO_IMAGE_MEAN, W.DINO_IMAGE_STD))
+
+
+def _same_size(u, size, path):
+    if u.shape != size:
+        raise ValueError(f"{path}: image of {u.shape[1]}x{u.shape[0]} in a prompt folder of {size[1]}x{size[0]} images "
+                         "(the images of one prompt must share one size)")
 
 
 def _decode(path):
@@ -173,9 +305,16 @@ def _decode(path):
         return np.asarray(im.convert("RGB"))
 
 
-def main(args, face_provider=None, log=print):
+def main(args, face_provider=None, log=print, cfgs=None):
     if not torch.cuda.is_available():
         raise RuntimeError("finetune_fair_diffusion_amd.evaluate_images needs an MI355X (HIP device); there is no CPU path")
+    original_dir = getattr(args, "original_imgs_dir", None)
+    pairs = None
+    if original_dir is not None:          # both refusals come before any device work and before anything is written
+        if not args.synthetic and not (os.environ.get("FD_CLIP_VISION_DIR") and os.environ.get("FD_DINO_WEIGHTS")):
+            raise FileNotFoundError("--original_imgs_dir needs FD_CLIP_VISION_DIR (CLIP ViT-H/14 directory) and FD_DINO_WEIGHTS "
+                                    "(dinov2_vitb14_pretrain.pth), as training's image regularisers do (pass --synthetic for synthetic weights)")
+        pairs = pair_paths(args.generated_imgs_dir, original_dir)
     from PIL import Image
     from . import ops
     from .classifier import MobileNetV3Large
@@ -200,22 +339,28 @@ def main(args, face_provider=None, log=print):
             from .pretrained import load_classifier
             sd = load_classifier(path, ATTR_K[which])
         classifiers.append(MobileNetV3Large(sd, device, ATTR_K[which]))
+    clip, dino = _load_encoders(args, _default_cfgs(cfgs), device) if pairs is not None else (None, None)
 
     labels = IndexLabels(args.index_font, getattr(args, "index_font_size", LABEL_FONT_SIZE)) if getattr(args, "index_font", None) and args.grid != "off" else None
-    folders = _numbered(glob.glob(os.path.join(args.generated_imgs_dir, "prompt_*")), lambda x: int(x.split("_")[-1]))
+    folders = _prompt_folders(args.generated_imgs_dir)
     os.makedirs(args.save_dir, exist_ok=True)
     results = [{}, {}, {}, {}, {}]          # indicators, boxes, gender / race / age logits
     metrics = {}
+    semantics, numbers = [{}, {}], {}       # CLIP / DINOv2 similarities and the image numbers they belong to (--original_imgs_dir)
     n_images, t0 = 0, time.time()
     with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
         for folder in folders:
-            prompt_idx = int(folder.split("_")[-1])
-            paths = _numbered(glob.glob(os.path.join(folder, "img_*.jpg")), lambda x: int(x.split("_")[-1].split(".")[0]))
+            prompt_idx = _prompt_number(folder)
+            paths = _image_paths(folder)
             if not paths:
                 continue
             decoded = pool.map(_decode, paths)          # submitted now, consumed in order: decoding runs ahead of the device work
             imgs_d, ind_p, boxes_p, logits_p = [], [], [], [[], [], []]
             size = None
+            if pairs is not None:
+                paths_o = [o for _, o in pairs[prompt_idx]]
+                assert [g for g, _ in pairs[prompt_idx]] == paths, (prompt_idx, "the generated tree changed after it was paired")
+                decoded_o, size_o, sims_p = pool.map(_decode, paths_o), None, []
             for b0 in range(0, len(paths), args.batch_size):
                 bp = paths[b0:b0 + args.batch_size]
                 batch = []
@@ -223,9 +368,7 @@ def main(args, face_provider=None, log=print):
                     u = next(decoded)
                     if size is None:
                         size = u.shape
-                    if u.shape != size:
-                        raise ValueError(f"{path}: image of {u.shape[1]}x{u.shape[0]} in a prompt folder of {size[1]}x{size[0]} images "
-                                         "(the images of one prompt must share one size)")
+                    _same_size(u, size, path)
                     batch.append(u)
                 u8 = torch.from_numpy(np.stack(batch))                       # [b,H,W,3] uint8
                 u8_d = u8.to(device, non_blocking=False)
@@ -236,6 +379,15 @@ def main(args, face_provider=None, log=print):
                 chips = ops.crop_resize_u8(u8_d, boxes.to(device), -1.0, args.size_face)
                 for k, clf in enumerate(classifiers):
                     logits_p[k].append(clf(chips).float())
+                if pairs is not None:
+                    batch_o = []
+                    for path in paths_o[b0:b0 + args.batch_size]:
+                        u = next(decoded_o)
+                        if size_o is None:
+                            size_o = u.shape
+                        _same_size(u, size_o, path)
+                        batch_o.append(u)
+                    sims_p.append(torch.stack(pair_similarity(clip, dino, u8_d, torch.from_numpy(np.stack(batch_o)).to(device))))
                 imgs_d.append(u8_d)
                 ind_p.append(ind)
                 boxes_p.append(boxes)
@@ -253,6 +405,10 @@ def main(args, face_provider=None, log=print):
             results[1][prompt_idx] = boxes.to(torch.int64)
             for k in range(3):
                 results[2 + k][prompt_idx] = logits[k].cpu()
+            if pairs is not None:
+                sims = torch.cat(sims_p, dim=1).cpu()          # [2, N] fp32: the prompt's one copy
+                semantics[0][prompt_idx], semantics[1][prompt_idx] = sims[0].clone(), sims[1].clone()
+                numbers[prompt_idx] = [_image_number(p) for p in paths]
             n_images += len(paths)
     with open(os.path.join(args.save_dir, "test_results.pkl"), "wb") as f:
         pickle.dump(results, f)
@@ -261,9 +417,17 @@ def main(args, face_provider=None, log=print):
            "mean": {k: float(np.array([m[k] for m in metrics.values()]).mean()) for k in keys}}
     with open(os.path.join(args.save_dir, "metrics.json"), "w") as f:
         json.dump(_json_safe(out), f, indent=1)
+    if pairs is not None:
+        with open(os.path.join(args.save_dir, "semantics.pkl"), "wb") as f:
+            pickle.dump(semantics, f)
+        with open(os.path.join(args.save_dir, "semantics.json"), "w") as f:
+            json.dump(semantics_summary(semantics, numbers), f, indent=1)
     dt = time.time() - t0
     if log is not None:
-        log(json.dumps({"evaluated_images": n_images, "prompts": len(metrics), "seconds": round(dt, 3), "images_per_s": round(n_images / dt, 2) if dt > 0 else None}))
+        line = {"evaluated_images": n_images, "prompts": len(metrics), "seconds": round(dt, 3), "images_per_s": round(n_images / dt, 2) if dt > 0 else None}
+        if pairs is not None:
+            line["semantics_pairs"] = n_images
+        log(json.dumps(line))
     return results, out
 
 
