@@ -30,7 +30,6 @@ __device__ __forceinline__ f32x16 zero16() {
 // congruent mod 8: an XCD then holds the K / V of the few heads it is working on instead of every XCD holding every head's.
 __device__ __forceinline__ void attn_block_coords(int nblk, int H, int B, int& b, int& h, int& blk) {
     const int L = blockIdx.x, NH = H * B;
-#ifndef FD_ATTN_NO_XCD_MAP
     if ((NH & 7) == 0) {
         const int xcd = L & 7, m = L >> 3;
         blk = m % nblk;
@@ -39,7 +38,6 @@ __device__ __forceinline__ void attn_block_coords(int nblk, int H, int B, int& b
         h = hh - b * H;
         return;
     }
-#endif
     blk = L % nblk;
     const int hh = L / nblk;
     b = hh / H;
@@ -70,6 +68,24 @@ __device__ __forceinline__ f16x8 read_tr(const f16* tile, int stride, int k0, in
 // row stride (halfs) of a tile that is only read with read_tr: the 32 lanes serviced together fetch 4 rows x 64 bytes, which sit on distinct
 // banks when the stride is 64 or 192 bytes modulo 256
 constexpr int tr_stride(int DV) { return DV % 128 == 32 || DV % 128 == 96 ? DV : (DV + 32) % 128 == 32 || (DV + 32) % 128 == 96 ? DV + 32 : DV + 64; }
+
+// Tile geometry of head dim D: the ONE copy behind the kernels' LDS pointers and the byte counts the launchers ask for.  Every tile holds 64 rows;
+// offsets and strides are in halfs.
+template <int D> struct AttnTile {
+    static constexpr int DK = (D + 15) / 16 * 16, DV = (D + 31) / 32 * 32;      // D padded for a contraction over d / where d is an output dimension
+    static constexpr int NKS = DK / 16, NDV = DV / 32;                         // k-steps of such a contraction / 32-row output tiles
+    // forward: K [64][DKP], then V [64][VP] (V is only read through read_tr)
+    static constexpr int DKP = DK + 8, VP = tr_stride(DV);
+    static constexpr int FWD_V = 64 * DKP;
+    static constexpr size_t FWD_LDS = (size_t)(FWD_V + 64 * VP) * sizeof(f16);
+    // backward: two tiles [64][BWD_DKP] (dQ: K, V; dK/dV: Q, dO), both read as fragments and through read_tr, whose reads run up to TR_SLACK halfs past
+    // the second tile's last row; behind the slack the dK/dV kernel keeps lse and D of the tile's 64 query rows (fp32)
+    static constexpr int BWD_DKP = DK + FD_ATTN_BWD_PAD;
+    static constexpr int BWD_2ND = 64 * BWD_DKP, TR_SLACK = 64;
+    static constexpr int BWD_STATS = 2 * BWD_2ND + TR_SLACK;
+    static constexpr size_t DQ_LDS = (size_t)BWD_STATS * sizeof(f16);
+    static constexpr size_t DKDV_LDS = DQ_LDS + 2 * 64 * sizeof(float);
+};
 
 
 // ---- register-staged tiles with the load split from the LDS write (issue the next tile's global loads before
@@ -128,11 +144,7 @@ __device__ __forceinline__ void zero_row_pad(f16* dst) {
 // each head-dim class reaches WITHOUT scratch (checked on the gfx950 ISA: .amdhsa_next_free_vgpr / private_segment_fixed_size).
 constexpr int fwd_waves(int D) { return D <= 64 ? 3 : D <= 128 ? 2 : 1; }
 constexpr int dq_waves(int D) { return D <= 40 ? 3 : D <= 128 ? 2 : 1; }
-#ifdef FD_DKDV_TR_W3      // measurement: dK/dV at d = 40 squeezed to three waves per SIMD (168 registers + 124 B of scratch)
-constexpr int dkdv_waves(int D) { return D == 40 ? 3 : D <= 64 ? 2 : 1; }
-#else
-constexpr int dkdv_waves(int D) { return D <= 64 ? 2 : 1; }
-#endif
+constexpr int dkdv_waves(int D) { return D <= 64 ? 2 : 1; }      // three at d = 40 (168 registers + 124 B of scratch) lost: profiles/r03_attention_dkdv_variants_rejected.txt
 
 // ---- "-D through the matrix pipe" (round 4).  dS = P o (dP - D), D = rowsum(dO o O): where the contraction over d is padded (d = 40 -> 48: eight spare
 // k-slots behind column 39) the subtraction rides in the dP = dO . V^T MFMAs: three slots of the dO operand carry -D split into three 16-bit
@@ -147,13 +159,7 @@ constexpr int dkdv_waves(int D) { return D <= 64 ? 2 : 1; }
 template <int D> constexpr bool pre_ok() { return D % 16 == 8; }
 #define FD_PRE_MASKED 30000.f        // "lse" of an invalid query row in the pre-scaled backward: exp2(s - 30000) == 0, and it splits into finite pieces
 
-template <int D> constexpr bool dfold() {
-#ifdef FD_ATTN_NO_DFOLD
-    return false;
-#else
-    return D % 16 == 8;      // lane-half 1 of the last k-step holds columns D .. D + 7: all padding
-#endif
-}
+template <int D> constexpr bool dfold() { return D % 16 == 8; }      // lane-half 1 of the last k-step holds columns D .. D + 7: all padding
 __device__ __forceinline__ void split3(float x, f16& h0, f16& h1, f16& h2) {
     h0 = (f16)x;
     const float r1 = x - (float)h0;
@@ -192,13 +198,12 @@ __global__ __launch_bounds__(256, QB == 1 ? fwd_waves(D) : (D <= 64 ? 2 : 1)) vo
                                                        f16* __restrict__ O, float* __restrict__ LSE, int H, int Tq, int Tk,
                                                        int Tkr, int kv_div, float scale, int ldq, int ldk) {
     FD_WG_TRACE(7);
-    constexpr int DK = (D + 15) / 16 * 16, DV = (D + 31) / 32 * 32, DKP = DK + 8;
-    constexpr int NKS = DK / 16, NDV = DV / 32;
+    using T = AttnTile<D>;
+    constexpr int DV = T::DV, DKP = T::DKP, VP = T::VP, NKS = T::NKS, NDV = T::NDV;
     constexpr int RB = 128 * QB;                // query rows per workgroup
     extern __shared__ __attribute__((aligned(16))) f16 smem[];
-    constexpr int VP = tr_stride(DV);
     f16* Ks = smem;               // [64][DKP]
-    f16* Vts = smem + 64 * DKP;   // [64][VP], keys x d
+    f16* Vts = smem + T::FWD_V;   // [64][VP], keys x d
 
     int b, h, qblk;
     attn_block_coords((Tq + RB - 1) / RB, H, gridDim.x / (((Tq + RB - 1) / RB) * H), b, h, qblk);
@@ -247,11 +252,7 @@ __global__ __launch_bounds__(256, QB == 1 ? fwd_waves(D) : (D <= 64 ? 2 : 1)) vo
     // Head dims with a spare padded output row (40, 80, 16): "V column D" is a column of ones, so row D of O^T accumulates sum_k p -- the softmax
     // denominator comes out of the P.V MFMAs (with the same rescaling as O) instead of 32 VALU adds and a shuffle per tile; it is the sum of
     // the fp16-rounded probabilities the numerator is built from.
-#ifdef FD_ATTN_NO_ONES
-    constexpr bool ONES = false;
-#else
     constexpr bool ONES = D < DV;
-#endif
     if (PRE) {
         __syncthreads();                               // behind zero_row_pad's writes of the same columns
         for (int c = threadIdx.x; c < 64 * 3; c += 256) Ks[(c / 3) * DKP + D + c % 3] = (f16)1.f;   // never overwritten: store_rows writes columns < D
@@ -464,11 +465,11 @@ __global__ __launch_bounds__(256, dq_waves(D)) void attn_bwd_dq_kernel(const f16
                                                           const f16* __restrict__ O, int H, int Tq, int Tk, int Tkr, int kv_div,
                                                           float scale, int ldq, int ldkv, int lddq) {
     FD_WG_TRACE(8);
-    constexpr int DK = (D + 15) / 16 * 16, DV = (D + 31) / 32 * 32, DKP = DK + FD_ATTN_BWD_PAD;
-    constexpr int NKS = DK / 16, NDV = DV / 32;
+    using T = AttnTile<D>;
+    constexpr int DKP = T::BWD_DKP, NKS = T::NKS, NDV = T::NDV;
     extern __shared__ __attribute__((aligned(16))) f16 smem[];
     f16* Ks = smem;                // [64][DKP]
-    f16* Vs = Ks + 64 * DKP;       // [64][DKP]
+    f16* Vs = smem + T::BWD_2ND;   // [64][DKP], then T::TR_SLACK
 
     int b, h, qblk;
     attn_block_coords((Tq + 127) / 128, H, gridDim.x / (((Tq + 127) / 128) * H), b, h, qblk);
@@ -619,13 +620,13 @@ __global__ __launch_bounds__(256, dkdv_waves(D)) void attn_bwd_dkdv_kernel(const
     FD_WG_TRACE(9);
     // ATOMIC + slab > 0: no atomics -- sample j of a K/V group stores its fp32 partial into slab j (slab = elements per [Bk*Tkr, lddkv] buffer);
     // the caller sums the kv_div slabs in a fixed order (fd_sum_slabs): bit-reproducible shared dK / dV
-    constexpr int DK = (D + 15) / 16 * 16, DV = (D + 31) / 32 * 32, DKP = DK + FD_ATTN_BWD_PAD;
-    constexpr int NKS = DK / 16, NDV = DV / 32;
+    using T = AttnTile<D>;
+    constexpr int DKP = T::BWD_DKP, NKS = T::NKS, NDV = T::NDV;
     extern __shared__ __attribute__((aligned(16))) f16 smem[];
     f16* Qs = smem;                 // [64][DKP]
-    f16* Gs = Qs + 64 * DKP;        // [64][DKP]  (dO rows)
-    float* lse_s = (float*)(Gs + 64 * DKP + 64);  // [64]  (64 halfs of slack: read_tr runs past the last row)
-    float* dd_s = lse_s + 64;                // [64]
+    f16* Gs = smem + T::BWD_2ND;    // [64][DKP]  (dO rows), then T::TR_SLACK
+    float* lse_s = (float*)(smem + T::BWD_STATS);   // [64]
+    float* dd_s = lse_s + 64;                       // [64]
 
     int b, h, kblk;
     attn_block_coords((Tk + 127) / 128, H, gridDim.x / (((Tk + 127) / 128) * H), b, h, kblk);
@@ -713,43 +714,6 @@ __global__ __launch_bounds__(256, dkdv_waves(D)) void attn_bwd_dkdv_kernel(const
             dv[i] = mfma32(ga, pf[st], dv[i]);
             dk[i] = mfma32(qa, dsf[st], dk[i]);
         };
-#ifdef FD_DKDV_PIPE
-        // measurement: both score tiles first, then the second tile's softmax interleaved with the first tile's dV / dK products
-        f32x16 s2[2], dp2[2];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            s2[qt] = zero16(); dp2[qt] = zero16();
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const f16x8 qa = *(const f16x8*)(Qs + (qt * 32 + kl) * DKP + ks * 16 + g * 8);
-                const f16x8 ga = *(const f16x8*)(Gs + (qt * 32 + kl) * DKP + ks * 16 + g * 8);
-                s2[qt] = mfma32(qa, kf[ks], s2[qt]);
-                dp2[qt] = mfma32(ga, vf[ks], dp2[qt]);
-            }
-        }
-        if (PF && q0 + 64 < Tq) {
-            load_rows<D>(qreg, Qb, ldq, q0 + 64, Tq);
-            load_rows<D>(greg, Gb, C, q0 + 64, Tq);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) soft(s2[0], dp2[0], 0, r);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int r = 4 * c; r < 4 * c + 4; ++r) soft(s2[1], dp2[1], 1, r);
-            if (NDV == 2) dvdk(c >> 1, c & 1);
-            else if (c < 2) {
-#pragma unroll
-                for (int i = 0; i < NDV; ++i) dvdk(c, i);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int st = 2; st < 4; ++st)
-#pragma unroll
-            for (int i = 0; i < NDV; ++i) dvdk(st, i);
-#else
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             f32x16 s = zero16(), dp = zero16();
@@ -771,7 +735,6 @@ __global__ __launch_bounds__(256, dkdv_waves(D)) void attn_bwd_dkdv_kernel(const
         for (int st = 0; st < 4; ++st)
 #pragma unroll
             for (int i = 0; i < NDV; ++i) dvdk(st, i);
-#endif
     }
     if (kvalid) {
         const int64_t off = ((int64_t)bk * Tkr + key) * lddkv + h * D;
@@ -804,94 +767,70 @@ __global__ __launch_bounds__(256, dkdv_waves(D)) void attn_bwd_dkdv_kernel(const
 }
 
 // ================================================================================== host side
-// Query blocks per wave of the forward (1 or 2).  FD_ATTN_FWD_QB (bench-hooks build only) forces a value for A/B.
-#ifdef FD_BENCH_HOOKS
-#include <stdlib.h>
-static inline const char* bench_env_attn(const char* n) { return getenv(n); }
-#else
-static inline const char* bench_env_attn(const char*) { return nullptr; }
-#endif
-#ifndef FD_ATTN_FWD_QB2
-#define FD_ATTN_FWD_QB2 1        // shipped policy: two query blocks per wave for long sequences of the small head dims (0: always one)
-#endif
+// Query blocks per wave of the forward (1 or 2): two for the long self-attention sequences of the small head dims, which halves the LDS fragment
+// traffic and the K / V staging per query (see attn_fwd_kernel); short sequences keep one (more workgroups, three waves per SIMD).
+// FD_ATTN_FWD_QB (bench-hooks build only) forces a value for A/B.
 static int fwd_qb(int d, int Tq, int Tk, int BH) {
     // measured, B16 H8 T4096 d40 (profiles/r04_attention_fwd_lazy_qb_ab.txt): 660 us (one block, eager reference point) -> 632 (lazy) -> 593 (lazy, two blocks);
     // T = 1024 / d = 80 and the 77-key cross attention do not gain (kept at one block)
-    int qb = (FD_ATTN_FWD_QB2 && d <= 64 && Tq >= 2048 && Tk >= 2048 && (long)BH * ((Tq + 255) / 256) >= 128) ? 2 : 1;
-    static const char* e = bench_env_attn("FD_ATTN_FWD_QB");
+    int qb = (d <= 64 && Tq >= 2048 && Tk >= 2048 && (long)BH * ((Tq + 255) / 256) >= 128) ? 2 : 1;
+    static const char* e = bench_env("FD_ATTN_FWD_QB");
     if (e) qb = atoi(e) == 2 && d <= 64 ? 2 : 1;
     return qb;
 }
 
-template <int D> static constexpr size_t fwd_lds() {
-    constexpr int DKP = (D + 15) / 16 * 16 + 8, DV = (D + 31) / 32 * 32;
-    return (size_t)(64 * DKP + 64 * tr_stride(DV)) * 2;
-}
-template <int D> static constexpr size_t dq_lds() {
-    constexpr int DKP = (D + 15) / 16 * 16 + FD_ATTN_BWD_PAD;
-    return (size_t)(2 * 64 * DKP + 64) * 2;      // + slack for the transpose reads that run past the last row
-}
-template <int D> static constexpr size_t dkdv_lds() {
-    constexpr int DKP = (D + 15) / 16 * 16 + FD_ATTN_BWD_PAD;
-    return (size_t)(2 * 64 * DKP + 64) * 2 + 512;   // + the same slack + lse_s, dd_s
-}
+// the shape check of the three entry points
+static bool attn_shape_ok(int B, int H, int Tq, int Tk, int Tkr, int kv_div) { return B > 0 && H > 0 && Tq > 0 && Tk > 0 && Tkr >= Tk && kv_div >= 1; }
 
-#define FD_DISPATCH_D(d, CALL)                                                       \
-    switch (d) {                                                                     \
-        case 16: { CALL(16); break; }                                                \
-        case 32: { CALL(32); break; }                                                \
-        case 40: { CALL(40); break; }                                                \
-        case 64: { CALL(64); break; }                                                \
-        case 80: { CALL(80); break; }                                                \
-        case 128: { CALL(128); break; }                                              \
-        case 160: { CALL(160); break; }                                              \
-        default: fd_set_error("attention: unsupported head dim %d", d); return FD_ERR_ARG; \
+// The dispatch of the three entry points: launch(Int<D>, bool_constant<PRE>) with the head dim and "q arrives pre-scaled" (the entry point's negative
+// ``scale``) as types.  A launch lambda holds only its entry point's own choice (QB, or ATOMIC) and the launch itself.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F>
+static int attn_dispatch(const char* who, int d, bool pre, F&& launch) {
+    FD_REQUIRE(!pre || d % 16 == 8, "%s: pre-scaled q (negative scale) needs d %% 16 == 8", who);
+    auto at = [&](auto D) {
+        if constexpr (pre_ok<decltype(D)::value>()) {
+            if (pre) return launch(D, std::true_type{});
+        }
+        return launch(D, std::false_type{});
+    };
+    switch (d) {
+        case 16: at(Int<16>{}); break;
+        case 32: at(Int<32>{}); break;
+        case 40: at(Int<40>{}); break;
+        case 64: at(Int<64>{}); break;
+        case 80: at(Int<80>{}); break;
+        case 128: at(Int<128>{}); break;
+        case 160: at(Int<160>{}); break;
+        default: fd_set_error("attention: unsupported head dim %d", d); return FD_ERR_ARG;
     }
-
-// raise the dynamic-LDS cap once per kernel instantiation (each macro expansion has its own static)
-#define ALLOW_LDS(kern, bytes)                                                                                   \
-    {                                                                                                            \
-        static bool once = false;                                                                                \
-        if (!once) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
-            once = true;                                                                                         \
-        }                                                                                                        \
-    }
+    return fd_check_launch(who);
+}
 
 extern "C" int fd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Tq, int Tk, int Tkr,
                            int d, int kv_div, float scale, int ldq, int ldk, void* stream) {
     if (ldq <= 0) ldq = H * d;
     if (ldk <= 0) ldk = H * d;
     FD_REQUIRE((ldq & 7) == 0 && (ldk & 7) == 0, "fd_attn_fwd: row strides must be multiples of 8");
-    FD_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0 && Tkr >= Tk && kv_div >= 1, "fd_attn_fwd: bad shape");
-    // 64 queries per wave (QB = 2) for the long self-attention sequences of the small head dims: halves the LDS fragment traffic and the K / V
-    // staging per query (see attn_fwd_kernel).  Short sequences keep QB = 1 (more workgroups, three waves per SIMD).
+    FD_REQUIRE(attn_shape_ok(B, H, Tq, Tk, Tkr, kv_div), "fd_attn_fwd: bad shape");
     const int qb = fwd_qb(d, Tq, Tk, B * H);
-    dim3 grid(((Tq + 128 * qb - 1) / (128 * qb)) * H * B);
+    const dim3 grid(((Tq + 128 * qb - 1) / (128 * qb)) * H * B);
     // scale < 0: q arrives multiplied by |scale| * log2(e) (fd_gemm_desc.colscale in the projection) -- see "pre-scaled q" above
     const bool pre = scale < 0.f;
     scale = fabsf(scale);
-    FD_REQUIRE(!pre || d % 16 == 8, "fd_attn_fwd: pre-scaled q (negative scale) needs d %% 16 == 8");
-#define LAUNCH_F(DD, QBV, PREV)                                                                                                \
-    {                                                                                                                          \
-        ALLOW_LDS((attn_fwd_kernel<DD, QBV, PREV>), (fwd_lds<DD>()));                                                          \
-        hipLaunchKernelGGL((attn_fwd_kernel<DD, QBV, PREV>), grid, dim3(256), (fwd_lds<DD>()), (hipStream_t)stream,            \
-                           (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, lse, H, Tq, Tk, Tkr, kv_div, scale, ldq, ldk); \
-    }
-#define CALL(DD)                                                             \
-    if constexpr (pre_ok<DD>()) {                                            \
-        if (pre) {                                                           \
-            if (qb == 2) LAUNCH_F(DD, (DD <= 64 ? 2 : 1), true)              \
-            else LAUNCH_F(DD, 1, true)                                       \
-            break;                                                           \
-        }                                                                    \
-    }                                                                        \
-    if (qb == 2 && DD <= 64) LAUNCH_F(DD, (DD <= 64 ? 2 : 1), false)         \
-    else LAUNCH_F(DD, 1, false)
-    FD_DISPATCH_D(d, CALL)
-#undef CALL
-#undef LAUNCH_F
-    return fd_check_launch("fd_attn_fwd");
+    return attn_dispatch("fd_attn_fwd", d, pre, [&](auto DD, auto PRE) {
+        auto go = [&](auto QB) {
+            constexpr auto kern = attn_fwd_kernel<DD(), QB(), PRE()>;
+            constexpr size_t lds = AttnTile<DD()>::FWD_LDS;
+            fd_allow_lds<kern>(lds);
+            hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, lse, H, Tq, Tk, Tkr,
+                               kv_div, scale, ldq, ldk);
+        };
+        if constexpr (DD() <= 64) {          // the head dims fwd_qb sends to two blocks
+            if (qb == 2) return go(Int<2>{});
+        }
+        go(Int<1>{});
+    });
 }
 
 extern "C" int fd_attn_bwd_prep(const void* o, const void* d_o, float* D, int B, int H, int T, int d, void* stream) {
@@ -910,30 +849,17 @@ extern "C" int fd_attn_bwd_dq(const void* q, const void* k, const void* v, const
     if (ldkv <= 0) ldkv = H * d;
     if (lddq <= 0) lddq = H * d;
     FD_REQUIRE((ldq & 7) == 0 && (ldkv & 7) == 0 && (lddq & 3) == 0, "fd_attn_bwd_dq: row strides");
-    FD_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0 && Tkr >= Tk && kv_div >= 1, "fd_attn_bwd_dq: bad shape");
-    dim3 grid(((Tq + 127) / 128) * H * B);
+    FD_REQUIRE(attn_shape_ok(B, H, Tq, Tk, Tkr, kv_div), "fd_attn_bwd_dq: bad shape");
+    const dim3 grid(((Tq + 127) / 128) * H * B);
     const bool pre = scale < 0.f;                    // q arrives multiplied by |scale| * log2(e): see "pre-scaled q"
     scale = fabsf(scale);
-    FD_REQUIRE(!pre || d % 16 == 8, "fd_attn_bwd_dq: pre-scaled q (negative scale) needs d %% 16 == 8");
-#define LAUNCH_Q(DD, PREV)                                                                                                             \
-    {                                                                                                                                  \
-        ALLOW_LDS((attn_bwd_dq_kernel<DD, PREV>), (dq_lds<DD>()));                                                                     \
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, PREV>), grid, dim3(256), (dq_lds<DD>()), (hipStream_t)stream, (const f16*)q,        \
-                           (const f16*)k, (const f16*)v, (const f16*)d_o, lse, D, (f16*)dq, (const f16*)o, H, Tq, Tk, Tkr, kv_div,     \
-                           scale, ldq, ldkv, lddq);                                                                                    \
-    }
-#define CALL(DD)                      \
-    if constexpr (pre_ok<DD>()) {     \
-        if (pre) {                    \
-            LAUNCH_Q(DD, true)        \
-            break;                    \
-        }                             \
-    }                                 \
-    LAUNCH_Q(DD, false)
-    FD_DISPATCH_D(d, CALL)
-#undef CALL
-#undef LAUNCH_Q
-    return fd_check_launch("fd_attn_bwd_dq");
+    return attn_dispatch("fd_attn_bwd_dq", d, pre, [&](auto DD, auto PRE) {
+        constexpr auto kern = attn_bwd_dq_kernel<DD(), PRE()>;
+        constexpr size_t lds = AttnTile<DD()>::DQ_LDS;
+        fd_allow_lds<kern>(lds);
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (const f16*)d_o, lse, D, (f16*)dq,
+                           (const f16*)o, H, Tq, Tk, Tkr, kv_div, scale, ldq, ldkv, lddq);
+    });
 }
 
 extern "C" int fd_attn_bwd_dkdv(const void* q, const void* k, const void* v, const void* d_o,
@@ -943,34 +869,25 @@ extern "C" int fd_attn_bwd_dkdv(const void* q, const void* k, const void* v, con
     if (ldkv <= 0) ldkv = H * d;
     if (lddkv <= 0) lddkv = H * d;
     FD_REQUIRE((ldq & 7) == 0 && (ldkv & 7) == 0 && (lddkv & 3) == 0, "fd_attn_bwd_dkdv: row strides");
-    FD_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0 && Tkr >= Tk && kv_div >= 1, "fd_attn_bwd_dkdv: bad shape");
-    dim3 grid(((Tk + 127) / 128) * H * B);
+    FD_REQUIRE(attn_shape_ok(B, H, Tq, Tk, Tkr, kv_div), "fd_attn_bwd_dkdv: bad shape");
+    const dim3 grid(((Tk + 127) / 128) * H * B);
     // accumulate == 2: fp32 per-sample slabs instead of atomics (dk, dv: [kv_div][Bk*Tkr][lddkv] fp32, every element written)
     const int64_t slab = accumulate == 2 ? (int64_t)(B / kv_div) * Tkr * lddkv : 0;
     FD_REQUIRE(accumulate != 2 || (B % kv_div) == 0, "fd_attn_bwd_dkdv: B must be a multiple of kv_div");
     // scale < 0: q arrives multiplied by |scale| * log2(e) ("pre-scaled q"): dK = scale * dS^T . q = dS^T . q' / log2(e)
     const bool pre = scale < 0.f;
     scale = pre ? 1.f / LOG2E : scale;
-    FD_REQUIRE(!pre || d % 16 == 8, "fd_attn_bwd_dkdv: pre-scaled q (negative scale) needs d %% 16 == 8");
-#define LAUNCH(DD, AT, PREV)                                                                                                           \
-    {                                                                                                                                  \
-        ALLOW_LDS((attn_bwd_dkdv_kernel<DD, AT, PREV>), (dkdv_lds<DD>()));                                                             \
-        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, AT, PREV>), grid, dim3(256), (dkdv_lds<DD>()), (hipStream_t)stream,               \
-                           (const f16*)q, (const f16*)k, (const f16*)v, (const f16*)d_o, lse, D, dk,                                   \
-                           dv, H, Tq, Tk, Tkr, kv_div, scale, ldq, ldkv, lddkv, slab);                                                 \
-    }
-#define CALL(DD)                                                     \
-    if constexpr (pre_ok<DD>()) {                                    \
-        if (pre) {                                                   \
-            if (kv_div > 1 || accumulate) LAUNCH(DD, true, true) else LAUNCH(DD, false, true) \
-            break;                                                   \
-        }                                                            \
-    }                                                                \
-    if (kv_div > 1 || accumulate) LAUNCH(DD, true, false) else LAUNCH(DD, false, false)
-    FD_DISPATCH_D(d, CALL)
-#undef CALL
-#undef LAUNCH
-    return fd_check_launch("fd_attn_bwd_dkdv");
+    return attn_dispatch("fd_attn_bwd_dkdv", d, pre, [&](auto DD, auto PRE) {
+        auto go = [&](auto ATOMIC) {          // fp32 dk / dv: atomics, or slabs where slab > 0
+            constexpr auto kern = attn_bwd_dkdv_kernel<DD(), ATOMIC(), PRE()>;
+            constexpr size_t lds = AttnTile<DD()>::DKDV_LDS;
+            fd_allow_lds<kern>(lds);
+            hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (const f16*)d_o, lse, D, dk, dv,
+                               H, Tq, Tk, Tkr, kv_div, scale, ldq, ldkv, lddkv, slab);
+        };
+        if (kv_div > 1 || accumulate) go(std::true_type{});
+        else go(std::false_type{});
+    });
 }
 
 FD_WGT_SETTER(attn)

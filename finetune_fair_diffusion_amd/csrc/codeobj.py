@@ -2,7 +2,8 @@
 splits the library's .hip_fatbin into its per-translation-unit offload bundles, unbundles the gfx950 ELF of each and returns the
 disassembly and the kernel resource notes.  Used by tests/test_cpu.py to hold two build invariants: no packed-fp32 VALU instruction in any
 shipped kernel ("the round-3 hazard"), and the register / scratch budgets of the hot kernels.
-``python codeobj.py --diff OLD.so NEW.so`` compares two builds kernel by kernel (how a refactor of the GEMM family shows that it left the ISA alone)."""
+``python codeobj.py --diff OLD.so NEW.so [REGEX]`` compares two builds kernel by kernel (how a refactor shows that it left the ISA alone) and exits 1
+if any kernel symbol -- or, with REGEX, any symbol it matches -- differs or exists on one side only."""
 import os
 import re
 import subprocess
@@ -71,7 +72,6 @@ def packed_f32_sites(lib_path):
     return sites
 
 
-GEMM_FAMILY = re.compile(r"gemm_\w*kernel|conv_halo_kernel|splitk_reduce_kernel")
 _SYMBOL = re.compile(r"^[0-9a-f]+ <(\S+)>:")
 _ADDRESS = re.compile(r"^\s*[0-9a-f]+:\s+")
 
@@ -93,9 +93,12 @@ def kernel_instructions(lib_path):
     return {k: "\n".join(v) for k, v in out.items()}
 
 
-def diff(old_lib, new_lib):
-    """Prints, per kernel symbol, identical / differs (instruction counts, resources) / only in OLD|NEW; -> number of GEMM-family symbols not identical."""
+def diff(old_lib, new_lib, only=None):
+    """Prints, per kernel symbol, identical / differs (instruction counts, resources) / only in OLD|NEW; -> number of symbols that are not identical or
+    exist on one side only.  ``only``: a regular expression; symbols it does not match anywhere are left out of the comparison."""
     old, new = kernel_instructions(old_lib), kernel_instructions(new_lib)
+    if only:
+        old, new = ({k: v for k, v in d.items() if re.search(only, k)} for d in (old, new))
     res = {}
     for tag, lib in (("old", old_lib), ("new", new_lib)):
         for _, co in code_objects(lib):
@@ -109,16 +112,18 @@ def diff(old_lib, new_lib):
             verdict = "identical"
         else:
             verdict = f"differs ({old[sym].count(chr(10)) + 1} -> {new[sym].count(chr(10)) + 1} instructions)  old {res.get(('old', sym))}  new {res.get(('new', sym))}"
-        bad += verdict != "identical" and bool(GEMM_FAMILY.search(sym))
+        bad += verdict != "identical"
         print(f"{verdict:12s} {sym}" if verdict == "identical" else f"{sym}: {verdict}")
-    print(f"{len(old)} -> {len(new)} symbols, {bad} GEMM-family symbols not identical")
+    print(f"{len(old)} -> {len(new)} kernel symbols{f' matching {only!r}' if only else ''}, {bad} not identical or on one side only")
     return bad
 
 
 if __name__ == "__main__":
     import sys
     if sys.argv[1:2] == ["--diff"]:
-        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
+        if len(sys.argv) not in (4, 5):
+            sys.exit("usage: codeobj.py --diff OLD.so NEW.so [REGEX]")
+        sys.exit(1 if diff(*sys.argv[2:]) else 0)
     for lib in sys.argv[1:]:
         s = packed_f32_sites(lib)
         print(f"{lib}: {len(s)} packed-fp32 VALU instructions" + (f", e.g. {s[0]}" if s else ""))

@@ -48,6 +48,23 @@ int fd_check_launch(const char* what);
                    "include/fairdiff_hip.h and set struct_size = sizeof(" #type ")",                                                         \
                (ptr) ? (int)(ptr)->struct_size : -1, (int)sizeof(type), FD_ABI_VERSION)
 
+// Environment switches of the measurement build (-DFD_BENCH_HOOKS, ``make BENCH_HOOKS=1``; scratch/README.md).  In the product library a stray
+// environment variable can neither change a tile policy nor skip work: every switch reads as unset.
+#ifdef FD_BENCH_HOOKS
+#include <stdlib.h>
+static inline const char* bench_env(const char* name) { return getenv(name); }
+#else
+static inline const char* bench_env(const char*) { return nullptr; }
+#endif
+
+// raise a kernel's dynamic-LDS cap above the 64 KB default, once per kernel instantiation (each has its own static; a function-local static's
+// initialisation is also safe when two host threads make the first launch at the same time)
+template <auto KERNEL>
+static inline void fd_allow_lds(size_t bytes) {
+    static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    (void)once;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

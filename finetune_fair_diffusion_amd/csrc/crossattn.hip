@@ -257,18 +257,7 @@ __global__ __launch_bounds__(256, CrossCfg<C>::OCC) void cross_block_kernel(Cros
     // ---------------------------------------------------------------- P1: q = n2 . Wq^T, scaled into the exponent's domain -> tile
     f32x4 acc[TM][TN];
     const int n0 = wave * Cf::WN;
-#ifdef FD_CROSS_SKIP        // measurement builds only (scratch/r05_passes.sh o): phases left out, results meaningless
-    constexpr int SKIP = FD_CROSS_SKIP;
-#else
-    constexpr int SKIP = 0;
-#endif
-    if (!(SKIP & 2)) project<C, LORA>(acc, tile, a.wq, n0, l15, lg, tb, a.qu, a.ld_qu, a.rp);
-    else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){1.f, 1.f, 1.f, 1.f};
-    }
+    project<C, LORA>(acc, tile, a.wq, n0, l15, lg, tb, a.qu, a.ld_qu, a.rp);
     __syncthreads();                               // every wave has read all of n2
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -299,7 +288,7 @@ __global__ __launch_bounds__(256, CrossCfg<C>::OCC) void cross_block_kernel(Cros
 
     // ---------------------------------------------------------------- P2: attention over the <= 80 keys, heads 2 wave, 2 wave + 1; o overwrites q
 #pragma unroll 1
-    for (int hh = 0; hh < ((SKIP & 4) ? 0 : 2); ++hh) {
+    for (int hh = 0; hh < 2; ++hh) {
         const int c0 = (wave * 2 + hh) * D;       // first column of the head
         // K fragments [key tile][k-step]: lane (key = 16 kt + l15, k = 32 ks + 8 lg ..); k >= D and keys >= L are zero
         f16x8 kf[5][NKS];
@@ -404,7 +393,7 @@ __global__ __launch_bounds__(256, CrossCfg<C>::OCC) void cross_block_kernel(Cros
         lora_down<C>(tile, a.od, a.ld_od, a.rp, tb, REC ? a.to_out : nullptr, row0, wave, l15, lg);
         __syncthreads();
     }
-    if (!(SKIP & 8)) project<C, LORA>(acc, tile, a.wo, n0, l15, lg, tb, a.ou, a.ld_ou, a.rp);
+    project<C, LORA>(acc, tile, a.wo, n0, l15, lg, tb, a.ou, a.ld_ou, a.rp);
     __syncthreads();                               // every wave has read all of o
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -513,11 +502,7 @@ extern "C" int fd_cross_attn_block(const fd_cross_block_desc* dp, void* stream) 
 #define CROSS_LAUNCH(CC, LL, RR)                                                                                                        \
     {                                                                                                                                   \
         constexpr size_t lds = ((size_t)CrossCfg<CC>::BM * CrossCfg<CC>::LDT + (LL ? CrossCfg<CC>::BM * CROSS_LDB : 0)) * 2;            \
-        static bool once = false;                                                                                                       \
-        if (!once) {                                                                                                                    \
-            (void)hipFuncSetAttribute((const void*)cross_block_kernel<CC, LL, RR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            once = true;                                                                                                                \
-        }                                                                                                                               \
+        fd_allow_lds<cross_block_kernel<CC, LL, RR>>(lds);                                                                              \
         hipLaunchKernelGGL((cross_block_kernel<CC, LL, RR>), grid, block, lds, (hipStream_t)stream, a);                                 \
     }
 #define CROSS_LAUNCH_C(CC)                                       \

@@ -521,8 +521,7 @@ static int launch_splitk_reduce(const fd_gemm_desc& d, hipStream_t s, int nsplit
 // the instantiations, in the order 0, 1, 2, 6, 3, 4: that order decides where each lands in the code object.)
 template <auto KERNEL, int NTHREADS, size_t LDS>
 static void launch_big_cv(const fd_gemm_desc& d, hipStream_t s, dim3 grid, int ntm, int ntn, int gn) {
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); });
+    fd_allow_lds<KERNEL>(LDS);
     hipLaunchKernelGGL(KERNEL, grid, dim3(NTHREADS), LDS, s, d, ntm, ntn, gn);
 }
 

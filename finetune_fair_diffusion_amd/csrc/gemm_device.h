@@ -6,19 +6,15 @@
 #include "common.h"
 #include <stdlib.h>
 #include <stdio.h>
-#include <mutex>
 
-// Measurement hooks (FD_GEMM_DBG sentinels inside the kernels, tile-policy A/B switches read from the environment) exist only in
-// builds made with -DFD_BENCH_HOOKS (``make BENCH_HOOKS=1``): in the product library a stray environment variable can neither
-// change tile selection nor skip work.
+// Measurement hooks: the FD_GEMM_DBG sentinels inside the kernels exist, like the tile-policy A/B switches read through bench_env (common.h), only in
+// builds made with -DFD_BENCH_HOOKS (``make BENCH_HOOKS=1``).
 #ifdef FD_BENCH_HOOKS
 #define FD_DBG_IS(p, v) ((p).batch == -(v))
 #define FD_DBG_GE(p, v) ((p).batch <= -(v))
-static inline const char* bench_env(const char* name) { return getenv(name); }
 #else
 #define FD_DBG_IS(p, v) false
 #define FD_DBG_GE(p, v) false
-static inline const char* bench_env(const char*) { return nullptr; }
 #endif
 
 // Can this launch use the LDS-staged fp16 epilogue (gemm_epilogue_lds)?  ONE definition for the kernels (which epilogue runs, i.e. whether statistics

@@ -203,11 +203,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(fd_gemm_desc p, int ntm,
 // the s_setprio form only (policy bit 4 of gemm.hip is on in every build since round 3; fd_gemm_kernel_name prints it so)
 template <int BM, int W, int CV>
 static void launch_halo(const fd_gemm_desc& d, hipStream_t s, int ntm, int ntn, int gn) {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)conv_halo_kernel<BM, W, CV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)halo_lds<BM, W>());
-    });
     constexpr size_t lds = halo_lds<BM, W>();
+    fd_allow_lds<conv_halo_kernel<BM, W, CV, true>>(lds);
     hipLaunchKernelGGL((conv_halo_kernel<BM, W, CV, true>), dim3(ntm * ntn), dim3(512), lds, s, d, ntm, ntn, gn);
 }
 

@@ -288,10 +288,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(fd_gemm_desc p, int ntm, i
 
 template <int BM, int CV, bool PRIO>
 static void launch_pp(const fd_gemm_desc& d, hipStream_t s, int ntm, int ntn, int gn, int nsplit) {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<BM, CV, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp_lds<BM>());
-    });
+    fd_allow_lds<gemm_pp_kernel<BM, CV, PRIO>>(pp_lds<BM>());
     hipLaunchKernelGGL((gemm_pp_kernel<BM, CV, PRIO>), dim3(ntm * ntn, nsplit), dim3(512), pp_lds<BM>(), s, d, ntm, ntn, gn);
 }
 

@@ -4,14 +4,6 @@
 
 #define GN_MAX_CHUNKS 64
 
-// A/B switches exist only in the bench-hooks build (make BENCH_HOOKS=1), as in gemm_device.h
-#ifdef FD_BENCH_HOOKS
-#include <cstdlib>
-static inline const char* bench_env(const char* name) { return getenv(name); }
-#else
-static inline const char* bench_env(const char*) { return nullptr; }
-#endif
-
 struct GNArgs {
     const f16* x1; const f16* x2; int C1, C2;
     const f16* dy;
@@ -632,15 +624,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const f16* x, const f16*
         }
     }
     f16x8 xv[R][MAXV], dv[BWD ? R : 1][MAXV];
-#ifdef FD_LN_ZERO_INIT      // measurement build (scratch/r05_passes.sh h): rules "a lane reads an uninitialised register" in or out of the packed-fp32 hazard
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i) {
-            xv[r][i] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            if (BWD) dv[r][i] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        }
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -730,15 +713,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const f16* x, const f16*
 template <bool BWD>
 static void launch_layernorm(hipStream_t s, const f16* x, const f16* dy, const float* gamma, const float* beta, const f16* add, f16* out,
                              float* mean_rstd, int M, int C, float eps) {
-#if defined(FD_LN_ONE_ROW)      // measurement: the one-row-per-wave form
-    constexpr int R1 = 1, R2 = 1, R4 = 1;
-#else
     // Both directions own 4 / 4 / 2 rows per wave.  (Round 3 shipped the backward at one row: its multi-row form made the three-stream
     // backward's gradients differ run to run.  Root cause, round 4: not a cross-stream race but packed-fp32 VALU code -- hipcc's SLP pass had
     // turned this kernel's per-element arithmetic into v_pk_{add,mul,fma}_f32, and those sequences returned wrong lanes whenever another
     // stream's kernel shared the SIMD; the library is built without packed-fp32 instructions since, csrc/Makefile.)
     constexpr int R1 = 4, R2 = 4, R4 = 2;
-#endif
     if (C <= 512) hipLaunchKernelGGL((layernorm_kernel<BWD, 1, R1>), dim3((M + 4 * R1 - 1) / (4 * R1)), dim3(256), 0, s, x, dy, gamma, beta, add, out, mean_rstd, M, C, eps);
     else if (C <= 1024) hipLaunchKernelGGL((layernorm_kernel<BWD, 2, R2>), dim3((M + 4 * R2 - 1) / (4 * R2)), dim3(256), 0, s, x, dy, gamma, beta, add, out, mean_rstd, M, C, eps);
     else hipLaunchKernelGGL((layernorm_kernel<BWD, 4, R4>), dim3((M + 4 * R4 - 1) / (4 * R4)), dim3(256), 0, s, x, dy, gamma, beta, add, out, mean_rstd, M, C, eps);

@@ -137,11 +137,7 @@ extern "C" int fd_small_attn_fwd(const void* q, const void* k, const void* v, vo
                                  int d, float scale, int causal, void* stream) {
     FD_REQUIRE(T >= 1 && T <= SA_MAXT && d >= 1 && d <= SA_MAXD, "fd_small_attn_fwd: T<=128, d<=128 (got T=%d d=%d)", T, d);
     const size_t lds = (size_t)(2 * T * (d + 1) + 4 * SA_MAXT + 4 * SA_MAXD) * sizeof(float);
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute((const void*)small_attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        once = true;
-    }
+    fd_allow_lds<small_attn_fwd_kernel>(160 * 1024);
     hipLaunchKernelGGL(small_attn_fwd_kernel, dim3(H, B), dim3(256), lds, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o,
                        P, key_valid, H, T, d, scale, causal);
     return fd_check_launch("fd_small_attn_fwd");
@@ -152,11 +148,7 @@ extern "C" int fd_small_attn_bwd(const void* q, const void* k, const void* v, co
     FD_REQUIRE(T >= 1 && T <= SA_MAXT && d >= 1 && d <= SA_MAXD, "fd_small_attn_bwd: T<=128, d<=128");
     const size_t lds = (size_t)(4 * T * (d + 1) + T * (T + 1)) * sizeof(float);
     FD_REQUIRE(lds <= 160 * 1024, "fd_small_attn_bwd: T=%d d=%d needs %zu B of LDS", T, d, lds);
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute((const void*)small_attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        once = true;
-    }
+    fd_allow_lds<small_attn_bwd_kernel>(160 * 1024);
     hipLaunchKernelGGL(small_attn_bwd_kernel, dim3(H, B), dim3(256), lds, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, P,
                        (const f16*)d_o, (f16*)dq, (f16*)dk, (f16*)dv, H, T, d, scale);
     return fd_check_launch("fd_small_attn_bwd");

@@ -148,11 +148,7 @@ template <typename XT, int CIN, int STRIDE, bool NCHW, bool HAS_ACT>
 static void launch_conv_small_fast_a(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int Cout, int Ho, int Wo,
                                    int act, hipStream_t s) {
     const size_t lds = (size_t)9 * CIN * Cout * sizeof(float);
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute((const void*)conv_small_cin_fast_kernel<XT, CIN, STRIDE, NCHW, HAS_ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        once = true;
-    }
+    fd_allow_lds<conv_small_cin_fast_kernel<XT, CIN, STRIDE, NCHW, HAS_ACT>>(160 * 1024);
     const int slots = 256 / (Cout / 8);
     const int64_t nq = (int64_t)B * Ho * ((Wo + 3) / 4);
     int64_t blocks = (nq + slots - 1) / slots;

@@ -3,7 +3,6 @@ pointers + the current HIP stream out.  torch is plumbing here (device memory, s
 every op fails loudly if the HIP library is missing or a kernel reports an error.
 """
 import ctypes
-import os
 import math
 
 import torch
@@ -85,12 +84,10 @@ class OpTimer:
 TIMER = None
 
 
-GN_STATS = os.environ.get("FD_NO_GN_STATS") is None      # A/B switch: GroupNorm statistics from the producer's epilogue (fd_gemm_desc.gn_stats)
-
 def _gemm_call(d, conv, out=None, gn_stats=False):
     ws = gemm_workspace()
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    if gn_stats and GN_STATS:
+    if gn_stats:        # GroupNorm statistics from the producer's epilogue (fd_gemm_desc.gn_stats)
         # the kernel fd_gemm picks decides the chunk height (its wave-tile rows); 0 = no statistics epilogue for this problem.  The buffer rides on
         # the output tensor OBJECT: ``groupnorm`` finds it there, and anything that makes a new tensor of the output (cat, slicing) drops it
         rows = _lib.get().fd_gemm_stats_rows(ctypes.byref(d))
@@ -253,7 +250,6 @@ def conv3x3(x, w, B, H, W, *, mode=CONV_NORMAL, bias=None, rowbias=None, residua
 
 CONV_UP2P, CONV_UP2P_BWD, CONV_UP2PI = 4, 5, 6
 _BIG_TILES = (256320, 128320, 128160, 256128, 256256, 512128)
-_NO_UP2P = os.environ.get("FD_NO_UP2P") is not None      # A/B switch: nearest-up2 convs as 3x3 gathers at the high resolution
 
 
 def _up2p_desc(x, w, out, B, H, W, Cin, Cout, bwd, bias=None):
@@ -276,7 +272,7 @@ def conv_up2(x, conv, B, H, W):
     """Upsample2D: conv3x3(nearest-up2(x)) + bias.  x [B*H*W, Cin] -> ([B*2H*2W, Cout], 2H, 2W).  Evaluated as four 2x2-tap phase problems
     over the low-res input (4/9 of the multiply-adds) when the big-tile kernels take the shape, else as a 3x3 gather at the high resolution."""
     Cin, Cout = conv.cin, conv.cout
-    if not _NO_UP2P and Cin % 64 == 0 and Cout % 8 == 0:
+    if Cin % 64 == 0 and Cout % 8 == 0:
         out = torch.empty((4 * B * H * W, Cout), dtype=F16, device=x.device)
         # the four phases go straight into the channels-last result (FD_CONV_UP2PI: the epilogue maps rows), and the
         # epilogue leaves the GroupNorm statistics of the result behind in phase-major chunk order (``per`` = chunks per image and phase)
@@ -292,7 +288,7 @@ def conv_up2(x, conv, B, H, W):
 def conv_up2_bwd(dy, conv, B, H, W):
     """Input gradient of ``conv_up2``: dy [B*2H*2W, Cout] -> [B*H*W, Cin] (H, W = low resolution)."""
     Cin, Cout = conv.cin, conv.cout
-    if not _NO_UP2P and Cout % 64 == 0 and Cin % 8 == 0:
+    if Cout % 64 == 0 and Cin % 8 == 0:
         out = torch.empty((B * H * W, Cin), dtype=F16, device=dy.device)
         d = _up2p_desc(_chk(dy), conv.wd_up2p, out, B, H, W, Cout, Cin, True)
         if _lib.get().fd_gemm_tile(ctypes.byref(d)) % 1000000 in _BIG_TILES:
@@ -486,13 +482,12 @@ def to_f32(x, scale=1.0):
 LOG2E = 1.4426950408889634
 # "Pre-scaled q" (round 4): for head dims with spare contraction slots (d = 40) the projection writes q * (d^-0.5 * log2 e) -- in its fp32 epilogue, one
 # rounding as before (fd_gemm_desc.colscale) -- and the three attention kernels take the QK^T accumulator as the exponent's argument, the softmax
-# reference point / saved log-sum-exp riding in the spare slots (csrc/attn.hip).  FD_NO_PRESCALED_Q=1 restores the multiply-add per score element.
-PRESCALED_Q = os.environ.get("FD_NO_PRESCALED_Q") is None
+# reference point / saved log-sum-exp riding in the spare slots (csrc/attn.hip).  Other head dims keep the multiply-add per score element.
 
 
 def q_prescale(d):
     """Factor the q projection folds into its epilogue for head dim ``d``, or None where the attention kernels have no spare contraction slots."""
-    return (d ** -0.5) * LOG2E if (PRESCALED_Q and d % 16 == 8) else None
+    return (d ** -0.5) * LOG2E if d % 16 == 8 else None
 
 
 def attn_fwd(q, k, v, B, H, Tq, Tk, d, kv_div=1, scale=None, need_lse=False, kv_rows=None, prescaled=False):
@@ -556,18 +551,19 @@ def attn_bwd(q, k, v, o, do, lse, B, H, Tq, Tk, d, kv_div=1, scale=None, dk_acc=
     return dq, dk, dv
 
 
-# The cross-attention sub-block (LayerNorm2 -> to_q -> attention over the prompt tokens -> to_out + residual -> LayerNorm3) as one launch, for forwards
-# that neither record nor carry LoRA slabs (csrc/crossattn.hip).  FD_NO_FUSED_CROSS=1: the five separate launches.
-FUSED_CROSS = os.environ.get("FD_NO_FUSED_CROSS") is None
-FUSED_CROSS_TRAIN = os.environ.get("FD_NO_FUSED_CROSS_TRAIN") is None      # ... also where the forward carries LoRA slabs and / or records for the backward (R1 / R3)
+# The cross-attention sub-block (LayerNorm2 -> to_q -> attention over the prompt tokens -> to_out + residual -> LayerNorm3) as one launch
+# (csrc/crossattn.hip), with or without LoRA slabs and records for the backward; shapes it refuses take the five separate launches.
 CROSS_LP = 80          # key padding of the transposed V the fused kernel reads
 
 
-CROSS_WIDTHS = tuple(int(c) for c in os.environ.get("FD_FUSED_CROSS_C", "320,640").split(",") if c)      # measurement: which levels take the fused kernel
+def cross_shape_ok(C, heads, L):
+    """Can a transformer block of width ``C`` with ``L`` prompt tokens take the fused kernel at all (is its transposed V worth making)?"""
+    return C in (320, 640) and heads == 8 and L <= CROSS_LP
 
 
 def cross_block_ok(M, C, heads, L, rows_per_sample, rp=0):
-    return (FUSED_CROSS and rp in (0, 8, 16) and C in CROSS_WIDTHS and heads == 8 and C in (320, 640) and L <= CROSS_LP and M % 64 == 0 and rows_per_sample % 64 == 0)
+    """... and can this call: ``M`` rows in samples of ``rows_per_sample``, LoRA slabs of padded rank ``rp`` (0 = none)?"""
+    return cross_shape_ok(C, heads, L) and rp in (0, 8, 16) and M % 64 == 0 and rows_per_sample % 64 == 0
 
 
 def cross_attn_block(x, ln2, wq, k, vt, L, wo, bo, ln3, heads, rows_per_sample, kv_div, need_stats=False, lora_q=None, lora_o=None, record=False, q_prescaled=False):
@@ -608,14 +604,13 @@ def cross_attn_block(x, ln2, wq, k, vt, L, wo, bo, ln3, heads, rows_per_sample, 
 
 # ----------------------------------------------------------------------------- LoRA / scheduler / optimizer
 _WGRAD_PENDING = None      # list of (X, T, G, sn, sr, R, scale) while a ``wgrad_batch()`` context is open
-_WGRAD_BATCHING = os.environ.get("FD_NO_WGRAD_BATCH") is None     # A/B switch: 0 -> every weight gradient is its own launch pair
 WGRAD_MAX = 16
 
 
 def lora_wgrad(X, T, G, sn, sr, R, scale=1.0):
     """G[n*sn + r*sr] += scale * sum_m X[m,n] T[m,r].  Inside ``with wgrad_batch():`` the call is queued and executed with the other
     queued problems in one partial + one final launch when the context closes (the operands are kept alive until then)."""
-    if _WGRAD_BATCHING and _WGRAD_PENDING is not None and R <= 16 and X.shape[1] % 8 == 0 and X.stride(0) % 8 == 0:
+    if _WGRAD_PENDING is not None and R <= 16 and X.shape[1] % 8 == 0 and X.stride(0) % 8 == 0:
         _WGRAD_PENDING.append((X, T, G, sn, sr, R, scale))
         return
     M, N = X.shape

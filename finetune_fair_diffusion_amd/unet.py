@@ -124,7 +124,7 @@ class TransformerBlock:
         else:
             K, V = ops.gemm(enc, self.k2.w), ops.gemm(enc, self.v2.w)
         self.cross = dict(static=bool(static and lo is None), K=K, V=V, Bk=Bk, L=L, enc=enc, te=te)
-        if ops.FUSED_CROSS and L <= ops.CROSS_LP and self.C in ops.CROSS_WIDTHS and self.heads == 8:
+        if ops.cross_shape_ok(self.C, self.heads, L):
             # the one-launch cross-attention sub-block (ops.cross_attn_block) reads V transposed, keys zero-padded to 80: made once per rollout; a captured
             # forward holds its address like K's and V's
             self.cross["Vt80"] = ops.transpose_btc(V, Bk, L, self.C, ops.CROSS_LP, out=old.get("Vt80") if (static and old) else None)
@@ -172,7 +172,7 @@ class TransformerBlock:
         o, lse = ops.attn_fwd(q, k, v, B, h, HW, HW, d, 1, need_lse=True, prescaled=qs is not None)
         l2 = self.lora2
         cr = self.cross
-        if (not pair and cr.get("Vt80") is not None and self.q2.bias is None and self.o2.bias is not None and (ops.FUSED_CROSS_TRAIN or (not rec and l2 is None))
+        if (not pair and cr.get("Vt80") is not None and self.q2.bias is None and self.o2.bias is not None
                 and ops.cross_block_ok(B * HW, C, h, cr["L"], HW, l2.q.rp if l2 is not None else 0)):
             # norm2 -> attn2 (with its LoRA slabs) -> residual -> norm3 is ONE launch (csrc/crossattn.hip); a forward that does not record never sees n2, q2, o2 in
             # HBM, a recording one gets them written once for the backward

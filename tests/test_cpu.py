@@ -357,6 +357,26 @@ def test_integration_md_descriptor_mirror_matches_header_and_lib(tmp_path):
     assert L.fd_lora_refresh_multi(ctypes.byref(r), 1, None) == -1 and b"struct_size" in L.fd_last_error()
 
 
+def test_codeobj_diff_counts_every_kernel_symbol(monkeypatch, capsys):
+    """``codeobj.py --diff`` is how a refactor shows that it left the compiled kernels alone: its count (the exit status) covers every kernel symbol -- changed,
+    or present on one side only -- not one family, and the optional regular expression narrows it.  (The disassembly is stubbed: this is the counting.)"""
+    monkeypatch.syspath_prepend(os.path.join(os.path.dirname(HERE), "finetune_fair_diffusion_amd", "csrc"))
+    import codeobj
+    libs = {"old": {"gemm_big_kernel": "a\nb", "attn_fwd_kernel": "a\nb", "layernorm_kernel": "c", "gone_kernel": "d"},
+            "new": {"gemm_big_kernel": "a\nb", "attn_fwd_kernel": "a\nb\nc", "layernorm_kernel": "c", "added_kernel": "d"}}
+    monkeypatch.setattr(codeobj, "kernel_instructions", lambda path: dict(libs[path]))
+    monkeypatch.setattr(codeobj, "code_objects", lambda path: [])
+    assert codeobj.diff("old", "old") == 0
+    assert capsys.readouterr().out.splitlines()[-1] == "4 -> 4 kernel symbols, 0 not identical or on one side only"
+    assert codeobj.diff("old", "new") == 3                      # attn_fwd_kernel differs, gone_kernel and added_kernel are on one side
+    out = capsys.readouterr().out
+    assert "attn_fwd_kernel: differs (2 -> 3 instructions)" in out and "gone_kernel: only in OLD" in out and "added_kernel: only in NEW" in out
+    assert out.splitlines()[-1] == "4 -> 4 kernel symbols, 3 not identical or on one side only"
+    assert codeobj.diff("old", "new", r"gemm_\w*kernel|layernorm") == 0
+    assert capsys.readouterr().out.splitlines()[-1] == "2 -> 2 kernel symbols matching 'gemm_\\\\w*kernel|layernorm', 0 not identical or on one side only"
+    assert codeobj.diff("old", "new", "attn|gone") == 2
+
+
 def test_library_exports_every_header_symbol():
     from finetune_fair_diffusion_amd import lib
     protos = lib.parse_header()
@@ -375,6 +395,11 @@ def test_library_exports_every_header_symbol():
     assert L.fd_attn_fwd(one, one, one, one, None, 2, 8, 256, 256, 256, 80, 1, -0.1118, 0, 0, None) == -1 and b"pre-scaled q" in L.fd_last_error()
     assert L.fd_attn_bwd_dq(one, one, one, one, one, one, one, one, 2, 8, 256, 256, 256, 80, 1, -0.1118, 0, 0, 0, None) == -1 and b"pre-scaled q" in L.fd_last_error()
     assert L.fd_attn_bwd_dkdv(one, one, one, one, one, one, one, one, 2, 8, 256, 256, 256, 80, 1, -0.1118, 0, 0, 0, 0, None) == -1
+    # ... and so is a head dim outside {16, 32, 40, 64, 80, 128, 160}, by all three entry points, with or without the spare slots
+    for dd, sc in ((48, 0.144), (24, -0.204)):
+        assert L.fd_attn_fwd(one, one, one, one, None, 2, 8, 256, 256, 256, dd, 1, sc, 0, 0, None) == -1 and b"unsupported head dim %d" % dd in L.fd_last_error()
+        assert L.fd_attn_bwd_dq(one, one, one, one, one, one, one, one, 2, 8, 256, 256, 256, dd, 1, sc, 0, 0, 0, None) == -1 and b"unsupported head dim %d" % dd in L.fd_last_error()
+        assert L.fd_attn_bwd_dkdv(one, one, one, one, one, one, one, one, 2, 8, 256, 256, 256, dd, 1, sc, 0, 0, 0, 0, None) == -1 and b"unsupported head dim %d" % dd in L.fd_last_error()
     d = lib.GemmDesc()
     d.A = d.B = d.C = 1 << 20
     d.M, d.N, d.K, d.batch, d.ldc, d.lda, d.ldb, d.colscale_cols = 300, 320, 320, 1, 320, 320, 320, 6

@@ -548,6 +548,12 @@ def test_attention_with_prescaled_q(ops, dev, B, H, Tq, Tk, kv_div):
         assert torch.equal(dq, dq2)
         check("attn dk fp16 (pre-scaled q)", dk2.reshape(Bk, Tk, C), kr.grad, 5e-3)
         check("attn dv fp16 (pre-scaled q)", dv2.reshape(Bk, Tk, C), vr.grad, 5e-3)
+    else:       # shared K / V through the atomics form (a backward without per-timestep slabs: accumulators zeroed by the caller)
+        dka, dva = torch.zeros_like(dko), torch.zeros_like(dvo)
+        dq4, _, _ = ops.attn_bwd(q2, k2, v2, o, do.reshape(B * Tq, C), lse, B, H, Tq, Tk, d, kv_div, dk_acc=dka, dv_acc=dva, prescaled=True)
+        assert torch.equal(dq, dq4)
+        check("attn dk atomics (pre-scaled q)", dka.reshape(Bk, Tk, C), kr.grad, 5e-3)
+        check("attn dv atomics (pre-scaled q)", dva.reshape(Bk, Tk, C), vr.grad, 5e-3)
 
 
 @pytest.mark.parametrize("gscale", [1.0, 1e-3, 1e-4])
