@@ -93,6 +93,39 @@ def kernel_instructions(lib_path):
     return {k: "\n".join(v) for k, v in out.items()}
 
 
+def _strip_signature(demangled):
+    """``void gemm_big_kernel<256, 320, 4, 4, 0>(fd_gemm_desc, int, int, int)`` -> ``gemm_big_kernel<256, 320, 4, 4, 0>``: the return type of a template
+    instantiation and the parameter list -- the LAST balanced parenthesis group -- dropped."""
+    name = demangled.strip()
+    if name.endswith(")"):
+        depth = 0
+        for k in range(len(name) - 1, -1, -1):
+            depth += (name[k] == ")") - (name[k] == "(")
+            if depth == 0:
+                name = name[:k]
+                break
+    return name[5:] if name.startswith("void ") else name
+
+
+def kernel_symbols(lib_path, only=None):
+    """-> sorted demangled kernel names of the library's gfx950 code objects, template arguments included and the parameter list dropped
+    (``gemm_big_kernel<256, 320, 4, 4, 0>``: how fd_gemm_kernel_name and rocprofv3 spell them).  ``only``: a regular expression the name must match.
+    A kernel is a function symbol whose mangled name has a kernel descriptor in the metadata notes (``kernel_resources``); its demangled spelling is the
+    one ``llvm-objdump -t --demangle`` prints for the function symbol at the SAME ADDRESS."""
+    kernels = set()
+    func = re.compile(r"^([0-9a-f]+)\s+\S+\s+F\s+\.text\s+[0-9a-f]+\s+(?:\.\w+\s+)?(.*)$")
+    for _, co in code_objects(lib_path):
+        mangled = set(kernel_resources(co))
+        tables = [subprocess.run([f"{LLVM}/llvm-objdump", "-t", *flag, co], capture_output=True, text=True, check=True).stdout for flag in ((), ("--demangle",))]
+        at = [{m.group(1): m.group(2) for m in map(func.match, t.splitlines()) if m} for t in tables]
+        for addr, sym in at[0].items():
+            if sym in mangled:
+                name = _strip_signature(at[1][addr])
+                if only is None or re.search(only, name):
+                    kernels.add(name)
+    return sorted(kernels)
+
+
 def diff(old_lib, new_lib, only=None):
     """Prints, per kernel symbol, identical / differs (instruction counts, resources) / only in OLD|NEW; -> number of symbols that are not identical or
     exist on one side only.  ``only``: a regular expression; symbols it does not match anywhere are left out of the comparison."""

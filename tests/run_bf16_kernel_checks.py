@@ -29,80 +29,33 @@ BF = torch.bfloat16
 GRID = 4096 * 256          # threads of a full grid-stride launch (elementwise.hip grid_for)
 
 # ============================================================================= bands
-B2_MARGIN = 1.25
+# tests/kernel_bands.py holds the bands, generic over the 16-bit dtype; these are its bf16 bindings under the names this script has always used.
+#   Gate A (coarse, every check): max|got - ref| <= tol * max|ref| with tol = 8 x the band of the matching fp16 test -- 8 = 2^-8 / 2^-11, the ratio of the
+#       unit roundoffs of bf16 and fp16 (the convention run_bf16_checks.py states).  fp32 outputs whose error does not pass through a stored bf16
+#       intermediate keep the fp16 test's band: fd_attn_bwd_prep, fd_patchify_bwd, fd_crop_resize_bwd, fd_warp_affine_bwd, fd_sum_slabs, the saved P of
+#       fd_small_attn_fwd, fd_lora_wgrad*, the GroupNorm statistics; so do ops whose operands are fp32 by the ABI (fd_cfg_dpm_step, fd_adamw_ema).
+#   Gate B (sharp; fp32 accumulation and ONE rounding to bf16: every fd_gemm path incl. convolutions, fd_lora_wgrad* and fd_attn_bwd_prep, whose fp32
+#       outputs take the fp32 half-ulp in place of the bf16 one and skip B2): B1 and B2 of kernel_bands.gate_b with roundings=1; the margin table is in
+#       the docstring of kernel_bands (bf16: ratio 1.000 at every K = 40 .. 11520 of this script, margin 1.25).
+#   Gate C (the other single-rounding ops): the elementwise maximum of |got - ref| / ulp_bf16(max(|ref|, floor)), floor = 2^-3 * rms(ref) unless the check
+#       states another, is printed and held to the value measured on the MI355X + 0.5 ulp (table GATE_C).  The reference rounded once to bf16 scores 0.5
+#       by construction: that is the yardstick, never the kernel's own output.
+import kernel_bands
+from kernel_bands import B2_MARGIN, coarse  # noqa: E402,F401
 
 
 def ulp_bf16(x):
     """Spacing of bf16 numbers at magnitude |x| (fp64 tensor): 2^(floor(log2|x|) - 7); below the smallest normal the subnormal spacing 2^-133."""
-    a = x.abs().double().clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(a)) - 7)
-
-
-def coarse(got, ref):
-    """Gate A statistic: max|got - ref| / max|ref|."""
-    got, ref = got.detach().double(), ref.detach().double()
-    return float((got - ref).abs().max() / (ref.abs().max() + 1e-300))
-
-
-def _b2_stat(x, ref, dim):
-    rms = ref.pow(2).mean(dim, keepdim=True).sqrt()
-    u = ulp_bf16(torch.maximum(ref.abs(), 0.125 * rms))
-    return ((x - ref) / u).pow(2).mean(dim).sqrt()
+    return kernel_bands.ulp(x, BF)
 
 
 def gate_b(got, ref, S, T, rounded=True):
-    """The bands of this script.
-
-    Gate A (coarse, every check): max|got - ref| <= tol * max|ref| with tol = 8 x the band of the matching fp16 test -- 8 = 2^-8 / 2^-11, the ratio
-    of the unit roundoffs of bf16 and fp16 (the convention run_bf16_checks.py states).  fp32 outputs whose error does not pass through a stored
-    bf16 intermediate keep the fp16 test's band: fd_attn_bwd_prep, fd_patchify_bwd, fd_crop_resize_bwd, fd_warp_affine_bwd, fd_sum_slabs, the saved
-    P of fd_small_attn_fwd, fd_lora_wgrad*, the GroupNorm statistics; so do ops whose operands are fp32 by the ABI (fd_cfg_dpm_step, fd_adamw_ema).
-
-    Gate B (sharp; fp32 accumulation and ONE rounding to bf16: every fd_gemm path incl. convolutions, fd_lora_wgrad* and fd_attn_bwd_prep, whose
-    fp32 outputs take the fp32 half-ulp in place of the bf16 one and skip B2).  Both parts must hold.
-      B1, elementwise:  |got - ref| <= 0.5 * ulp_bf16(max(|ref|, |got|)) + 2 * T * 2^-24 * S, S the statement on absolute values in fp64
-          (|A||B|^T + |A2||B2|^T + |bias| + |residual|), T the number of summed terms: the standard forward bound of T fp32 additions in any
-          order (T * u * S to first order), doubled because the MFMA's internal summation order and rounding are not specified.
-      B2, per row and per column:  rms((got - ref) / ulp_bf16(max(|ref|, 2^-3 * rms(ref of that row / column)))) <= B2_MARGIN x the same
-          statistic of ref.to(bfloat16) on the same data (about 0.29 = 1 / sqrt(12)).  The floor 2^-3 rms keeps elements that cancelled to
-          nearly zero, whose error is set by the larger terms that made them, from dominating the statistic.
-          Margin: the statistic of the fp32-accumulate emulation (torch fp32 matmul of the bf16 operands + second slab + bias + residual, rounded once)
-          over that of ref.to(bfloat16), largest over rows and columns, measured on the CPU (tests/test_bf16_bands_cpu.py recomputes and prints
-          them) at every GEMM-family K of this script:
-              K      40     64     288    320    336    576    640    1024   1280   2880   4104   5120   11520
-              ratio  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000  1.000
-          (the fp32 accumulation error is ~2^-16 of a bf16 ulp-sized step, so the emulation and the rounded reference differ only at near-ties)
-          margin = 1.25 x the largest (1.000) = 1.25; the 1.25 covers another summation order.  It is below 2, so the floor stands.
-
-    Gate C (the other single-rounding ops: norms, softmax, activations, GEGLU, attention outputs, elementwise families): the elementwise maximum of
-    |got - ref| / ulp_bf16(max(|ref|, floor)), floor = 2^-3 * rms(ref) unless the check states another, is printed and held to the value measured
-    on the MI355X + 0.5 ulp (table GATE_C).  The reference rounded once to bf16 scores 0.5 by construction: that is the yardstick, never the
-    kernel's own output.
-
-    Returns a dict: b1_bad (elements over the B1 band), b1_ratio (max |err| / band), b2_row / b2_col (largest ratio to the yardstick; None for
-    fp32 outputs)."""
-    got, ref, S = got.detach().double(), ref.detach().double(), S.detach().double()
-    err = (got - ref).abs()
-    half = 0.5 * ulp_bf16(torch.maximum(ref.abs(), got.abs())) if rounded else 2.0 ** -24 * torch.maximum(ref.abs(), got.abs())
-    band = half + 2.0 * T * 2.0 ** -24 * S
-    ratio = err / band.clamp_min(1e-300)
-    out = dict(b1_bad=int((err > band).sum()), b1_ratio=float(ratio.max()), b2_row=None, b2_col=None)
-    if rounded:
-        r2 = ref.reshape(-1, ref.shape[-1])
-        g2 = got.reshape(r2.shape)
-        yard = ref.to(BF).double().reshape(r2.shape)
-        for key, dim in (("b2_row", 1), ("b2_col", 0)):
-            out[key] = float((_b2_stat(g2, r2, dim) / _b2_stat(yard, r2, dim).clamp_min(0.05)).max())
-    out["ok_b1"] = out["b1_bad"] == 0 and math.isfinite(out["b1_ratio"])
-    out["ok_b2"] = (not rounded) or (out["b2_row"] <= B2_MARGIN and out["b2_col"] <= B2_MARGIN)
-    return out
+    """kernel_bands.gate_b for bf16, one rounding.  Returns a dict: b1_bad, b1_ratio, b2_row / b2_col (None for fp32 outputs), ok_b1, ok_b2."""
+    return kernel_bands.gate_b(got, ref, S, T, BF, rounded)
 
 
 def gate_c_stat(got, ref, floor=None):
-    got, ref = got.detach().double(), ref.detach().double()
-    if floor is None:
-        floor = 0.125 * float(ref.pow(2).mean().sqrt())
-    return float(((got - ref).abs() / ulp_bf16(ref.abs().clamp_min(max(floor, 2.0 ** -126)))).max())
+    return kernel_bands.gate_c_stat(got, ref, BF, floor)
 
 
 # Gate C table: check name -> (value measured on the MI355X in bf16 ulp, gate = measured + 0.5).  Rows over 2 ulp name the source.

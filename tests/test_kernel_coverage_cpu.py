@@ -198,3 +198,136 @@ def test_entry_points_tested_elsewhere_are_called_there():
         for h in helpers:           # one level of module-local helpers (``_device_targets``)
             called |= {c.func.attr for c in ast.walk(h) if isinstance(c, ast.Call) and isinstance(c.func, ast.Attribute)}
         assert {w for _, w in wr.get(name, ())} & called, f"{name}: tests/{mod}::{test} no longer calls its wrapper"
+
+
+# ============================================================================= the kernel instantiations behind fd_gemm
+# fd_gemm is ONE entry point with ~100 kernel symbols behind its dispatcher; the guard above counts it once.  tests/gemm_cases.py is the table of problems
+# that tests/test_kernels_sharp_gpu.py runs under the sharp gates; here, without a GPU, every gemm_* / conv_halo_* / splitk_* symbol of the built fp16 library
+# must be the kernel fd_gemm_kernel_name answers for at least one case, or be listed in gemm_cases.UNREACHED with a reason -- checked where it can be.
+GEMM_FAMILY = r"^(gemm_|conv_halo_|splitk_)"
+FP16_LIB = os.path.join(PKG, "libfairdiff_hip.so")
+
+
+def _fp16_lib():
+    """The fp16 product library with the header's prototypes bound (host-only queries: nothing here touches a device)."""
+    import ctypes
+    L = ctypes.CDLL(FP16_LIB)
+    for name, (ret, argtypes) in lib.parse_header().items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = ret, argtypes
+    assert L.fd_working_dtype().decode() == "fp16"
+    return L
+
+
+def _query(L, case, residual=True):
+    import ctypes
+    import gemm_cases
+    d = gemm_cases.descriptor(case, lib.GemmDesc, residual)
+    buf = ctypes.create_string_buffer(128)
+    split = L.fd_gemm_kernel_name(ctypes.byref(d), buf, 128)
+    return buf.value.decode(), split, L.fd_gemm_stats_rows(ctypes.byref(d)), L.fd_gemm_tile(ctypes.byref(d))
+
+
+def _shipped_gemm_symbols():
+    import sys
+    sys.path.insert(0, os.path.join(PKG, "csrc"))
+    import codeobj
+    return codeobj.kernel_symbols(FP16_LIB, GEMM_FAMILY)
+
+
+def _pp_default_policy():
+    import re
+    m = re.search(r"#define\s+FD_GEMM_PP_DEFAULT\s+\(([0-9 |]+)\)", open(os.path.join(PKG, "csrc", "gemm.hip")).read())
+    assert m, "FD_GEMM_PP_DEFAULT is no longer a plain OR of bits in csrc/gemm.hip"
+    bits = 0
+    for b in m.group(1).split("|"):
+        bits |= int(b)
+    return bits
+
+
+def test_every_case_of_the_gemm_table_names_the_kernel_the_dispatcher_picks():
+    import gemm_cases
+    L = _fp16_lib()
+    wrong = []
+    for c in gemm_cases.CASES:
+        for residual in ((True, False) if "R" in c.operands else (True,)):
+            name, split, rows, tile = _query(L, c, residual)
+            want_rows = 32 if c.gn_stats else None
+            if name != c.kernel or split != c.split or (want_rows is not None and rows != want_rows):
+                wrong.append(f"  {c.id} (residual={residual}): table says {c.kernel} split {c.split}, the library answers {name} split {split} (tile {tile}, stats rows {rows})")
+    assert not wrong, "the dispatch policy moved these cases of tests/gemm_cases.py (re-derive their shapes from gemm_tile's thresholds):\n" + "\n".join(wrong)
+
+
+def test_gemm_table_shapes_are_the_smallest_the_thresholds_admit():
+    """One row fewer and a big-tile / gemm_glds 128-row case lands on another kernel (skinny: M >= 1024, six rows of tail kept on purpose; the halo kernels
+    take whole images; the 64x64 tile and the small-M split-K branch have no lower threshold; convolution shapes are whole maps): the table tests tails, and stays as cheap as the dispatcher allows."""
+    import gemm_cases
+    L = _fp16_lib()
+    for c in gemm_cases.CASES:
+        floor_free = c.family == "skinny" or "<64, 64" in c.kernel or (c.split and "<128, 160" in c.kernel) or c.conv is not None
+        if floor_free:
+            continue
+        smaller = c._replace(M=c.M - 1)
+        name, split, _, _ = _query(L, smaller)
+        assert (name, split) != (c.kernel, c.split), f"{c.id}: M = {c.M - 1} still reaches {c.kernel}"
+
+
+def test_every_shipped_gemm_kernel_symbol_is_run_by_a_case_or_explained():
+    import gemm_cases
+    L = _fp16_lib()
+    symbols = _shipped_gemm_symbols()
+    assert len(symbols) > 90 and "splitk_reduce_kernel" in symbols and "gemm_skinny_kernel<1, 4, 1>" in symbols, symbols[:5]
+    named = set()
+    for c in gemm_cases.CASES:
+        name, split, _, _ = _query(L, c)
+        named.add(name)
+        if split > 1:
+            named.add("splitk_reduce_kernel")        # fd_gemm launches it behind every split-K GEMM
+    unexplained = [s for s in symbols if s not in named and s not in gemm_cases.UNREACHED]
+    assert not unexplained, ("kernel symbols of libfairdiff_hip.so that no case of tests/gemm_cases.py launches and UNREACHED does not explain:\n  " + "\n  ".join(unexplained))
+    both = sorted(named & set(gemm_cases.UNREACHED))
+    assert not both, f"listed as unreached but launched by a case (drop them from UNREACHED): {both}"
+    stale = sorted(s for s in gemm_cases.UNREACHED if s not in symbols)
+    assert not stale, f"UNREACHED names symbols the library no longer ships: {stale}"
+    never_unreached = [s for s in symbols if s.startswith("gemm_glds_kernel") or s.startswith("conv_halo_kernel") or (s.startswith("gemm_skinny_kernel") and s.endswith(", 1>"))]
+    assert len(never_unreached) == 6 + 12 + 12 and not set(never_unreached) & set(gemm_cases.UNREACHED)
+
+
+def test_reasons_of_the_unreached_gemm_kernels_hold_for_the_product_library():
+    import re
+    import gemm_cases
+    L = _fp16_lib()
+    assert set(gemm_cases.UNREACHED.values()) <= set(gemm_cases.REASONS)
+    used = set(gemm_cases.UNREACHED.values())
+    # "a bench_env switch of the measurement build": the product library has no bench hooks -- bench_env() returns nullptr there (csrc/common.h), the
+    # build string names none, and the one entry point only -DFD_BENCH_HOOKS exports is absent
+    if used & {"skinny_rt2", "w8", "pp_no_prio"}:
+        info = L.fd_build_info().decode()
+        assert "bench" not in info.lower() and "hook" not in info.lower(), info
+        assert not hasattr(L, "fd_bench_wg_trace"), "libfairdiff_hip.so was built with -DFD_BENCH_HOOKS: it is not the product library"
+        common = open(os.path.join(PKG, "csrc", "common.h")).read()
+        hooked, inert = "static inline const char* bench_env(const char* name) { return getenv(name); }", "static inline const char* bench_env(const char*) { return nullptr; }"
+        assert "#ifdef FD_BENCH_HOOKS" in common and 0 < common.index(hooked) < common.index(inert), "bench_env is no longer inert in product builds"
+        src = open(os.path.join(PKG, "csrc", "gemm.hip")).read()
+        assert 'bench_env("FD_GEMM_SKINNY_RT")' in src and 'bench_env("FD_GEMM_W8")' in src
+    # The ping-pong policy.  FD_GEMM_PP_DEFAULT can be overridden with -D (it sits behind #ifndef) and FD_GEMM_PP is read by a plain getenv that exists only
+    # under #ifdef FD_BENCH_HOOKS (pp_mode(), not bench_env): so the BUILT library is asked first, through fd_gemm_kernel_name, which prints pp_mode()'s bits --
+    # bit 4 as the last template argument, bits 2 / 16 / 64 as whether a dense 256x320, a dense 128x320 or a split-K problem lands on a ping-pong kernel.  The
+    # absence of fd_bench_wg_trace above (exported under the same macro) is what rules FD_GEMM_PP out; the parsed default below is the second witness.
+    by_id = {c.id: c for c in gemm_cases.CASES}
+    for cid in ("pp256 dense", "conv pp256", "conv pp128"):
+        assert _query(L, by_id[cid])[0].endswith(", true>"), f"{cid}: the built library's policy has bit 4 (s_setprio) off"
+    for cid, bit in (("big256x320", 2), ("big128x320", 16), ("split-K 128x320", 64)):
+        assert _query(L, by_id[cid])[0].startswith("gemm_big_kernel"), f"{cid}: the built library's policy has bit {bit} on: the ping-pong kernel takes it"
+    bits = _pp_default_policy()
+    assert bits & 4, "policy bit 4 (s_setprio) is off: the <..., false> ping-pong kernels are reachable and need cases"
+    assert not bits & 16 and not bits & 2 and not bits & 64, "dense GEMMs / split-K on the ping-pong tiles are now in the policy: they need cases"
+    # 16 waves for dense problems only: no conv or phase-pair case on the 256x320 tile may answer a 16-wave kernel
+    for c in gemm_cases.CASES:
+        if c.conv and "<256, 320" in c.kernel:
+            assert "<256, 320, 2, 4," in _query(L, c)[0], c.id
+    for s, why in gemm_cases.UNREACHED.items():
+        pattern = {"skinny_rt2": r"gemm_skinny_kernel<\d, \d, 2>$", "w8": r"gemm_big_kernel<(128, 320, 2, 4, \d|256, 320, 2, 4, [03])>$",
+                   "conv_16_waves": r"gemm_big_kernel<256, 320, 4, 4, [1246]>$", "pp_no_prio": r"gemm_pp_kernel<\d+, \d, false>$",
+                   "pp128_dense": r"gemm_pp_kernel<128, [02], true>$"}[why]
+        assert re.match(pattern, s), f"{s}: the reason {why!r} does not describe this symbol"
