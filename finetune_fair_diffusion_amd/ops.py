@@ -84,9 +84,10 @@ class OpTimer:
 TIMER = None
 
 
-def _gemm_call(d, conv, out=None, gn_stats=False):
-    ws = gemm_workspace()
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+def _gemm_call(d, conv, out=None, gn_stats=False, split_k=True):
+    if split_k:         # the dispatcher splits K only where it is handed a workspace
+        ws = gemm_workspace()
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
     if gn_stats:        # GroupNorm statistics from the producer's epilogue (fd_gemm_desc.gn_stats)
         # the kernel fd_gemm picks decides the chunk height (its wave-tile rows); 0 = no statistics epilogue for this problem.  The buffer rides on
         # the output tensor OBJECT: ``groupnorm`` finds it there, and anything that makes a new tensor of the output (cat, slicing) drops it
@@ -123,9 +124,10 @@ def _chk(t, dtype=F16):
 
 # ----------------------------------------------------------------------------- GEMM / conv
 def gemm(a, b, *, a2=None, b2=None, bias=None, rowbias=None, rows_per_batch=0, residual=None, act="none", alpha=1.0,
-         out=None, out_dtype=F16, n=None, aux=None, gn_stats=False, ln=None, colscale=None):
+         out=None, out_dtype=F16, n=None, aux=None, gn_stats=False, ln=None, colscale=None, split_k=True):
     """C[M,N] = act(alpha*(a.b^T + a2.b2^T) + bias + rowbias) + residual.  a:[M,K] (row stride free), b:[N,K].
-    act="geglu": b / bias rows interleaved (value_c, gate_c) -> C[M, N/2] = value * gelu(gate) (see ``interleave_geglu``)."""
+    act="geglu": b / bias rows interleaved (value_c, gate_c) -> C[M, N/2] = value * gelu(gate) (see ``interleave_geglu``).
+    ``split_k=False``: no split-K plan -- the kernel and k order the same product gets with an activation epilogue, which never splits."""
     M, K = a.shape
     N = b.shape[0] if n is None else n
     assert b.shape[1] == K and a.stride(1) == 1 and b.stride(1) == 1
@@ -152,7 +154,7 @@ def gemm(a, b, *, a2=None, b2=None, bias=None, rowbias=None, rows_per_batch=0, r
     if colscale is not None:        # (factor, columns): the first ``columns`` output columns times ``factor`` in fp32 before rounding (pre-scaled q)
         d.colscale, d.colscale_cols = colscale
     if ln is None:
-        _gemm_call(d, False, out, gn_stats)
+        _gemm_call(d, False, out, gn_stats, split_k)
         return out
     # ln = (gamma, beta, eps): also return LayerNorm(out) and its per-row statistics (fd_layernorm_fwd; the form that wrote them from the GEMM's own
     # epilogue was never a win inside the step and lives in scratch/gemm_ln_epilogue_experiment.h)

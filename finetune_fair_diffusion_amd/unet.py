@@ -227,8 +227,9 @@ class TransformerBlock:
         if proj is None:
             # lean recording (round 6): the 8C-wide pre-gate projection -- 40 % of a transformer block's recorded bytes -- and the LayerNorm outputs n1 / n2
             # (needed only by LoRA weight gradients) were not kept: recomputed here from the kept residual streams h2 / h0 / h1 by the SAME kernels the forward
-            # ran (LayerNorm, then the FF1 projection without its gate epilogue: same tile, same k order), hence bit-identical operands and gradients
-            proj = ops.gemm(ops.layernorm(c["h2"], self.ln3.gamma, self.ln3.beta, 1e-5), self.ff1_wi, bias=self.ff1_bi)
+            # ran (LayerNorm, then the FF1 projection without its gate epilogue: same tile, same k order), hence bit-identical operands and gradients.
+            # Without split-K: the GEGLU launch never splits, while the bare projection would at C = 1280 up to 256 rows (another kernel, another k order)
+            proj = ops.gemm(ops.layernorm(c["h2"], self.ln3.gamma, self.ln3.beta, 1e-5), self.ff1_wi, bias=self.ff1_bi, split_k=False)
         dproj = ops.geglu_bwd_interleaved(proj, dgg)
         del proj
         if self._ff1_wiT is None:
