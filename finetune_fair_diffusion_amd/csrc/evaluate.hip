@@ -1,8 +1,8 @@
 // Device tail of the in-training validation (evaluation.py; exp-1-debias-gender/1-main-debias.py evaluate_process :1449-1571, plot_in_grid :151-217):
 // the probability table of one validation prompt is reduced to integer counts, and the annotated image grid is painted as uint8, so that
 // only 32 integers and the finished grid cross to the host.  Neither kernel is on the training step's critical path.
-// The offline evaluator (evaluate_images.py; eval-generated-images.py) adds the two kernels that start from JPEG-decoded uint8 HWC images: the face-chip
-// crop (crop_face :296-319 on ``u/255*2-1``) and the two- / three-strip grid (plot_in_grid_gender_race :65-168, plot_in_grid_gender_race_age :171-263).
+// The offline evaluator (evaluate_images.py; eval-generated-images.py) adds the kernels that start from JPEG-decoded uint8 HWC images: the face-chip
+// crop (crop_face :296-319 on ``u/255*2-1``), the aligned face chip (image_pipeline :321-341) and the two- / three-strip grid (plot_in_grid_gender_race :65-168, plot_in_grid_gender_race_age :171-263).
 // The training monitor (step.py; exp-3 1-main-debias.py :1989-2002, :2063-2075, exp-4 :2088, :2176) paints the same two- / three-strip grid from the
 // working-dtype NCHW images the step holds.  The three painters share one tile geometry, outline, strip / bar rule, pixel rule and thread mapping
 // (the helpers below); they differ in the pixel fetch, and the one-strip painter in the colour of its outline and the form its bar arrives in.
@@ -274,6 +274,62 @@ extern "C" int fd_crop_resize_u8_fwd(const uint8_t* img, const int32_t* boxes, f
     hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, img, boxes, fill, (f16*)chips,
                        H, W, S, n);
     return fd_check_launch("fd_crop_resize_u8_fwd");
+}
+
+// ---------------------------------------------------------------- fd_warp_affine_u8_fwd
+// img [B,H,W,3] uint8 -> aligned chips [n,3,S,S] working dtype NCHW (and their horizontal mirrors): warp_affine_fwd_kernel (smallconv.hip) -- the same
+// map A[k] from output pixel (x, y, 1) to the sampling position and the same bilinear expression -- with the taps read from the bytes as ``u/255*2-1``.
+// Thread mapping of crop_resize_u8_kernel: one thread per output pixel, all three channels.  src_index is device memory nobody has validated: an entry
+// outside [0,B) makes its chip a chip of ``fill`` and reads no image byte.  A sampling position that does not fit an int (a malformed A) saturates in
+// the conversion and its taps fail the bounds test: they read ``fill``.
+__global__ __launch_bounds__(256) void warp_affine_u8_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ src_index, const float* __restrict__ A,
+                                                             float fill, f16* __restrict__ chips, f16* __restrict__ mirror, int B, int H, int W, int S, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % S);
+        const int64_t p = i / S;
+        const int oy = (int)(p % S);
+        const int64_t k = p / S;
+        const int b = src_index[k];
+        float v[3] = {fill, fill, fill};
+        if (b >= 0 && b < B) {
+            const float* a = A + k * 6;
+            const float xs = a[0] * ox + a[1] * oy + a[2], ys = a[3] * ox + a[4] * oy + a[5];
+            const float xf = floorf(xs), yf = floorf(ys);
+            const int x0 = (int)xf, y0 = (int)yf;
+            const float lx = xs - xf, ly = ys - yf;
+            const uint8_t* ip = img + (int64_t)b * H * W * 3;
+            float tap[4][3];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t yy = (int64_t)y0 + (q >> 1), xx = (int64_t)x0 + (q & 1);
+                const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+                const uint8_t* t = ip + (in ? (yy * W + xx) * 3 : 0);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) tap[q][c] = in ? eval_u8_unit(t[c]) : fill;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = bilinear_blend(ly, lx, tap[0][c], tap[1][c], tap[2][c], tap[3][c]);
+        }
+        const int64_t row = (k * 3 * S + oy) * S;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f16 h = (f16)v[c];
+            chips[row + (int64_t)c * S * S + ox] = h;
+            if (mirror) mirror[row + (int64_t)c * S * S + (S - 1 - ox)] = h;
+        }
+    }
+}
+
+extern "C" int fd_warp_affine_u8_fwd(const uint8_t* img, const int32_t* src_index, const float* A, float fill, void* chips, void* chips_mirror, int n_chips, int B,
+                                     int H, int W, int S, void* stream) {
+    FD_REQUIRE(img && src_index && A && chips, "fd_warp_affine_u8_fwd: null pointer");
+    FD_REQUIRE(n_chips >= 1 && B >= 1 && S >= 1 && S <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
+               "fd_warp_affine_u8_fwd: n_chips = %d, B = %d (supported >= 1 each), S = %d, H = %d, W = %d (supported 1..4096 each)", n_chips, B, S, H, W);
+    const int64_t n = (int64_t)n_chips * S * S;
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(warp_affine_u8_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, img, src_index, A, fill,
+                       (f16*)chips, (f16*)chips_mirror, B, H, W, S, n);
+    return fd_check_launch("fd_warp_affine_u8_fwd");
 }
 
 // ---------------------------------------------------------------- fd_eval_grid_attrs_u8, fd_eval_grid_attrs

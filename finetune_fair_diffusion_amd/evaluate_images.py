@@ -17,9 +17,10 @@ reads ``generated_imgs_dir/prompt_{i}/img_{j}.jpg`` (what ``generate.py`` writes
 Images are decoded on the host (PIL) by a small prefetch pool, uploaded as uint8 HWC and never converted as a whole: the face chips are cropped
 straight from the bytes (``ops.crop_resize_u8``: ``u/255*2-1`` in fp32 per tap, as the reference crops its fp32 tensor) and the grid is painted from
 the bytes with the reference's four fp32 roundings (``ops.eval_grid_attrs``).  An image without a face gets the all -1 chip and is classified like
-the others, as in the reference (:392, :643-645); only its indicator marks it.  The reference's aligned 112x112 chips are computed there but never
-saved: they are not built.  ``grid_attrs_host`` / ``grid_attrs_order`` are the plain host statements the grid kernel and the device ordering are
-tested against (tests/golden/reference_evalimages_grid.npz holds the reference's own arrays).
+the others, as in the reference (:392, :643-645); only its indicator marks it.  The reference's aligned 112x112 chips (:321-341, :401, :475) are
+computed there but never used or saved; here ``--face_metrics`` (below) builds them, from the bytes as well, for the face term's two similarities.
+``grid_attrs_host`` / ``grid_attrs_order`` are the plain host statements the grid kernel and the device ordering are tested against
+(tests/golden/reference_evalimages_grid.npz holds the reference's own arrays); ``warp_affine_u8_host`` is that of the aligned chips.
 
 ``--original_imgs_dir DIR`` (build addition) names a second tree of the same layout, written by ``generate.py`` from the same prompts file and seed
 without the LoRA files, so that ``prompt_{i}/img_{j}.jpg`` of both trees were drawn from the same noise.  Each pair is then compared the way training
@@ -32,6 +33,21 @@ regularises it: ``sim = <normalize(e_gen), normalize(e_ori)>`` of the CLIP ViT-H
 
 and leaves the three files above exactly as they are without it.  The encoders' weights come from ``FD_CLIP_VISION_DIR`` / ``FD_DINO_WEIGHTS`` as in
 training (``--synthetic``: ``synthetic_vit_state``).
+
+``--face_metrics`` (build addition) reports the third thing training regularises, face realism (``FairnessTrainer._face_term``, exp-1 :1917-1932): SFNet-20
+features of the landmark-aligned ``--size_aligned_face`` chip of every image with a face -- ``get_face_feats``: the chip plus its mirror, summed and
+L2-normalised in fp32 -- with the chips sampled straight from the bytes (``ops.warp_affine`` on the uint8 image: chips and mirrors in one launch).
+
+  * ``sim_face_real[j]`` -- the largest dot product with a row of the real-face database, ``1 - loss_face`` of training when the target is the nearest
+    real face (``nearest_face_similarity``: the search of ``FairnessTrainer.nearest_face_feats``, once per prompt);
+  * ``sim_face_ori[j]`` (with ``--original_imgs_dir``) -- ``<f_gen, f_ori>`` with the original image's own face, through the same provider, alignment
+    and network: ``1 - loss_face`` when the target class already matches.
+
+An image without a face -- for ``sim_face_ori``: a pair without two faces -- holds ``nan``, not the project's -1: both quantities live in [-1, 1], where
+-1 is a value a face can have.  It adds ``faces.pkl`` = ``[landmarks_all, sim_face_real_all, sim_face_ori_all]`` (prompt index -> CPU float32
+[N,5,2] / [N] / [N]; landmarks of an image without a face are -1; the third dict is empty without ``--original_imgs_dir``) and ``faces.json``
+(``faces_summary``), and leaves every other file as it is without it.  Weights: ``--opensphere_model_path`` / ``--face_feats_path`` as in training
+(``--synthetic``: ``synthetic_face_state`` / ``synthetic_face_db``).
 """
 import argparse
 import glob
@@ -57,6 +73,10 @@ DECODE_THREADS = 8                   # fixed: the pool only hides JPEG decoding 
 SYNTHETIC_SEEDS = (9101, 9102, 9103)
 SYNTHETIC_VIT_SEEDS = (21, 22)       # CLIP, DINOv2
 VIT_KEYS = ("clip_vision", "dino")
+SYNTHETIC_FACE_SEEDS = (9111, 9112)  # SFNet-20, the face database
+FACE_SHORTLIST = 8                   # candidates the fp16 scores hand to the fp32 choice (FairnessTrainer.nearest_face_feats)
+FACE_NET_DEFAULT = "./data/4-opensphere_checkpoints/opensphere_checkpoints/20220424_210641/models/backbone_100000.pth"
+FACE_DB_DEFAULT = "./data/3-face-features/CelebA_MobileNetLarge_08240859/face_feats.pkl"
 
 
 def parse_args(input_args=None):
@@ -75,12 +95,12 @@ def parse_args(input_args=None):
       default="./exp-3-debias-gender-race/outputs/from-paper_finetune-text-encoder_09190230/checkpoint-12200-generated-images/test_prompts_occupation_results")
     a("--batch_size", type=int, default=10, help="images per launch sequence (the reference evaluates one image at a time)")
     a("--size_face", type=int, default=224)
-    a("--size_aligned_face", type=int, default=112, help="accepted for the reference's command lines; the aligned chips are not built")
+    a("--size_aligned_face", type=int, default=112, help="side of the aligned face chips --face_metrics builds (a multiple of 16; the reference's command lines carry it)")
     a("--synthetic", action="store_true", default=False, help="(build addition) random classifier weights")
     a("--face_provider", type=str, default="synthetic", help="(build addition) 'synthetic' or 'detector', as in train.py")
     a("--grid", type=str, default="gender_race", choices=["gender_race", "gender_race_age", "off"],
       help="(build addition) which of the reference's two grids to paint; its main runs gender_race")
-    # the three flags below are absent from the namespace unless given (argparse.SUPPRESS): without them the arguments are the reference's plus --grid etc.
+    # the flags below are absent from the namespace unless given (argparse.SUPPRESS): without them the arguments are the reference's plus --grid etc.
     a("--index_font", type=str, default=argparse.SUPPRESS,
       help="(build addition) PATH of a TrueType font file, or 'default' for Pillow's embedded one: print each image's index on its tile as the reference "
            "does with Arial Bold; not given: no index text")
@@ -88,6 +108,11 @@ def parse_args(input_args=None):
     a("--original_imgs_dir", type=str, default=argparse.SUPPRESS,
       help="(build addition) a tree laid out like --generated_imgs_dir, generated from the same prompts and seed without the LoRA files: adds the CLIP / "
            "DINOv2 cosine similarity of every image pair (semantics.pkl, semantics.json); not given: no such files")
+    a("--face_metrics", action="store_true", default=argparse.SUPPRESS,
+      help="(build addition) SFNet-20 similarity of every aligned face to the nearest real face of --face_feats_path and, with --original_imgs_dir, to the "
+           "original image's face (faces.pkl, faces.json); not given: no such files")
+    a("--opensphere_model_path", type=str, default=argparse.SUPPRESS, help=f"(--face_metrics) SFNet-20 backbone, training's flag; default {FACE_NET_DEFAULT}")
+    a("--face_feats_path", type=str, default=argparse.SUPPRESS, help=f"(--face_metrics) face_feats.pkl of real faces, training's flag; default {FACE_DB_DEFAULT}")
     return p.parse_args(input_args) if input_args is not None else p.parse_args()
 
 
@@ -135,6 +160,33 @@ def grid_attrs_host(images, order, boxes, preds, bar_rows, palettes):
     images = np.asarray(images)
     x = torch.from_numpy(images).float() / 255 * 2 - 1
     return paint_attrs_tiles((x * 0.5 + 0.5).mul(255).to(torch.uint8).numpy(), order, boxes, preds, bar_rows, palettes)
+
+
+def warp_affine_u8_host(u8, src_index, A, S, fill=-1.0):
+    """The numpy fp64 statement of ``fd_warp_affine_u8_fwd``: u8 [B,H,W,3] uint8, src_index [n], A [n,6] (output pixel (x, y, 1) -> sampling position in
+    input pixels, ``fairness.alignment_sampling_matrix``) -> chips [n,3,S,S] float64.  A tap inside the image is ``u/255*2-1``, one outside is ``fill``;
+    bilinear weights from the fractional parts of the position; a ``src_index`` entry outside [0,B) gives a chip of ``fill``."""
+    u8 = np.asarray(u8)
+    B, H, W, _ = u8.shape
+    x = u8.astype(np.float64) / 255 * 2 - 1
+    A = np.asarray(A, dtype=np.float64).reshape(-1, 6)
+    oy, ox = np.mgrid[0:S, 0:S]
+    out = np.full((len(A), 3, S, S), float(fill))
+    for k, b in enumerate(np.asarray(src_index).reshape(-1).tolist()):
+        if not 0 <= b < B:
+            continue
+        a = A[k]
+        xs, ys = a[0] * ox + a[1] * oy + a[2], a[3] * ox + a[4] * oy + a[5]
+        x0, y0 = np.floor(xs), np.floor(ys)
+        lx, ly = (xs - x0)[..., None], (ys - y0)[..., None]
+
+        def tap(yy, xx):
+            inside = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+            v = x[b][np.clip(yy, 0, H - 1).astype(np.int64), np.clip(xx, 0, W - 1).astype(np.int64)]          # [S,S,3]
+            return np.where(inside[..., None], v, float(fill))
+        v = (1 - ly) * ((1 - lx) * tap(y0, x0) + lx * tap(y0, x0 + 1)) + ly * ((1 - lx) * tap(y0 + 1, x0) + lx * tap(y0 + 1, x0 + 1))
+        out[k] = v.transpose(2, 0, 1)
+    return out
 
 
 # ------------------------------------------------------------------------------------------ device side
@@ -293,6 +345,104 @@ def _load_encoders(args, cfgs, device):
             VisionTransformer(cfgs["dino"], sds[1], device, W.DINO_IMAGE_MEAN, W.DINO_IMAGE_STD))
 
 
+# ------------------------------------------------------------------------------------------ face realism and identity (--face_metrics)
+def synthetic_face_state(size_aligned_face=112):
+    """``--synthetic --face_metrics``: seeded random SFNet-20 weights for chips of ``size_aligned_face``, made as ``factory.build_trainer`` makes them."""
+    from . import weights as W
+    return W.synthetic_state_dict(W.sfnet20_param_shapes(in_size=size_aligned_face), seed=SYNTHETIC_FACE_SEEDS[0])
+
+
+def synthetic_face_db():
+    """``--synthetic --face_metrics``: 4096 seeded random unit vectors [4096,512] fp32, the stand-in of ``face_feats.pkl`` in ``factory.build_trainer``."""
+    return F.normalize(torch.randn(4096, 512, generator=torch.Generator().manual_seed(SYNTHETIC_FACE_SEEDS[1])), dim=-1)
+
+
+def _face_weight_paths(args):
+    """(SFNet path, database path) of a ``--face_metrics`` run with real weights; a missing file is refused here, before any device work or output."""
+    net, db = getattr(args, "opensphere_model_path", FACE_NET_DEFAULT), getattr(args, "face_feats_path", FACE_DB_DEFAULT)
+    missing = [f"--{flag} {path}" for flag, path in (("opensphere_model_path", net), ("face_feats_path", db)) if not os.path.isfile(path)]
+    if missing:
+        raise FileNotFoundError("--face_metrics needs the SFNet-20 backbone and the real-face feature file of training's face term; not found: "
+                                + ", ".join(missing) + " (pass --synthetic for synthetic weights)")
+    return net, db
+
+
+def _load_face_models(args, device):
+    """-> (SFNet20, database [M,512] fp32 unit rows on the device, its working-dtype copy for the MFMA scores)"""
+    from . import ops
+    from .sfnet import SFNet20
+    S = args.size_aligned_face
+    if args.synthetic:
+        sd, db = synthetic_face_state(S), synthetic_face_db()
+    else:
+        from .pretrained import load_face_db, load_face_net
+        net_path, db_path = _face_weight_paths(args)
+        sd, db = load_face_net(net_path, in_size=S), load_face_db(db_path)
+    db = F.normalize(db.to(device, torch.float32), dim=-1).contiguous()
+    return SFNet20(sd, device, in_size=S), db, db.to(ops.F16).contiguous()
+
+
+def face_features_u8(face_net, u8_d, ind, landmarks, S):
+    """``get_face_feats`` (:1176-1190) of the images with a face, from the bytes: u8_d [b,H,W,3] uint8 on the device, ind [b] bool and landmarks
+    [b,5,2] (x, y) on the host -> (rows: the images with a face, features [len(rows),512] fp32 unit vectors on the device), or ``([], None)`` when
+    no image has one (nothing is launched then).  One launch makes the aligned chips and their mirrors; SFNet runs on both and the sum is
+    L2-normalised in fp32."""
+    from . import ops
+    from .fairness import alignment_sampling_matrix
+    rows = ind.nonzero().view(-1).tolist()
+    if not rows:
+        return rows, None
+    H, W = u8_d.shape[1:3]
+    A = np.stack([alignment_sampling_matrix(landmarks[i].numpy(), H, W, S) for i in rows])
+    A = torch.tensor(A, dtype=torch.float32).to(u8_d.device)
+    idx = torch.tensor(rows, dtype=torch.int32).to(u8_d.device)
+    chips, mirrored = ops.warp_affine(u8_d, idx, A, S, mirror=True)
+    return rows, F.normalize(face_net.forward(chips).float() + face_net.forward(mirrored).float(), dim=-1)
+
+
+def nearest_face_similarity(db, db16, query):
+    """Largest dot product of each query [n,512] (fp32 unit rows on the device) with a row of the database ``db`` [M,512] fp32 (``db16``: its
+    working-dtype copy) -> [n] fp32: ``FaceFeatsModel.semantic_search`` (:98-117) as ``FairnessTrainer.nearest_face_feats`` runs it -- working-dtype MFMA
+    scores shortlist 8 rows per query, the winner is chosen among them in fp32 -- returning the winner's similarity instead of its row."""
+    from . import ops
+    n, M = query.shape[0], db.shape[0]
+    q16 = torch.zeros(((n + 7) // 8 * 8, query.shape[1]), dtype=ops.F16, device=query.device)
+    q16[:n] = query.to(ops.F16)
+    scores = ops.gemm(db16, q16, out_dtype=torch.float32)[:, :n].t()            # [n, M]
+    cand = scores.topk(min(FACE_SHORTLIST, M), dim=-1).indices
+    return (db[cand] * query[:, None, :]).sum(dim=-1).max(dim=-1).values
+
+
+def faces_summary(faces, image_numbers_by_prompt):
+    """The content of ``faces.json`` from the content of ``faces.pkl``: ``faces`` = [landmarks_all, sim_face_real_all, sim_face_ori_all] ({prompt
+    index: [N,5,2] / [N] / [N]}, ``nan`` = no face / no two-face pair; the third dict empty without ``--original_imgs_dir``),
+    ``image_numbers_by_prompt`` = {prompt index: the N numbers ``j`` of ``img_j.jpg``}.  Per prompt: ``faces`` (rows with a similarity to a real
+    face) and, over the rows that have the value, ``sim_face_*`` (mean), ``min_sim_face_*`` and ``argmin_face_*`` (the image NUMBER of the minimum, the
+    first one on a tie), null when no row has it; with originals also ``pairs`` (rows with two faces).  ``mean``: per quantity the mean of the per-prompt
+    means over the prompts that have one, null when none has."""
+    _, real_all, ori_all = faces
+    names = [("real", real_all)] + ([("ori", ori_all)] if ori_all else [])
+    per = {}
+    for i, numbers in image_numbers_by_prompt.items():
+        row = {}
+        for name, sims in names:
+            s = np.asarray(sims[i], dtype=np.float64).reshape(-1)
+            assert len(s) == len(numbers), (i, name, len(s), len(numbers))
+            have = np.nonzero(~np.isnan(s))[0]
+            row["faces" if name == "real" else "pairs"] = int(len(have))
+            if len(have):
+                first_min = have[int(s[have].argmin())]
+                row["sim_face_" + name], row["min_sim_face_" + name], row["argmin_face_" + name] = float(s[have].mean()), float(s[first_min]), int(numbers[first_min])
+            else:
+                row["sim_face_" + name] = row["min_sim_face_" + name] = row["argmin_face_" + name] = None
+        per[str(i)] = row
+    mean = {}
+    for name, _ in names:
+        vals = [m["sim_face_" + name] for m in per.values() if m["sim_face_" + name] is not None]
+        mean["sim_face_" + name] = float(np.mean(vals)) if vals else None
+    return _json_safe({"per_prompt": per, "mean": mean})
+
+
 def _same_size(u, size, path):
     if u.shape != size:
         raise ValueError(f"{path}: image of {u.shape[1]}x{u.shape[0]} in a prompt folder of {size[1]}x{size[0]} images "
@@ -306,6 +456,9 @@ def _decode(path):
 
 
 def main(args, face_provider=None, log=print, cfgs=None):
+    face_metrics = bool(getattr(args, "face_metrics", False))
+    if face_metrics and not args.synthetic:          # refused before any device work and before anything is written
+        _face_weight_paths(args)
     if not torch.cuda.is_available():
         raise RuntimeError("finetune_fair_diffusion_amd.evaluate_images needs an MI355X (HIP device); there is no CPU path")
     original_dir = getattr(args, "original_imgs_dir", None)
@@ -340,6 +493,7 @@ def main(args, face_provider=None, log=print, cfgs=None):
             sd = load_classifier(path, ATTR_K[which])
         classifiers.append(MobileNetV3Large(sd, device, ATTR_K[which]))
     clip, dino = _load_encoders(args, _default_cfgs(cfgs), device) if pairs is not None else (None, None)
+    face_net, face_db, face_db16 = _load_face_models(args, device) if face_metrics else (None, None, None)
 
     labels = IndexLabels(args.index_font, getattr(args, "index_font_size", LABEL_FONT_SIZE)) if getattr(args, "index_font", None) and args.grid != "off" else None
     folders = _prompt_folders(args.generated_imgs_dir)
@@ -347,6 +501,8 @@ def main(args, face_provider=None, log=print, cfgs=None):
     results = [{}, {}, {}, {}, {}]          # indicators, boxes, gender / race / age logits
     metrics = {}
     semantics, numbers = [{}, {}], {}       # CLIP / DINOv2 similarities and the image numbers they belong to (--original_imgs_dir)
+    faces, n_chips = [{}, {}, {}], 0        # landmarks, similarity to the nearest real face, to the original's face (--face_metrics)
+    S_al = args.size_aligned_face
     n_images, t0 = 0, time.time()
     with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
         for folder in folders:
@@ -361,6 +517,10 @@ def main(args, face_provider=None, log=print, cfgs=None):
                 paths_o = [o for _, o in pairs[prompt_idx]]
                 assert [g for g, _ in pairs[prompt_idx]] == paths, (prompt_idx, "the generated tree changed after it was paired")
                 decoded_o, size_o, sims_p = pool.map(_decode, paths_o), None, []
+            if face_metrics:          # per prompt: unit features [N,512] of the generated and the original faces, nan rows where there is none
+                lms_p = []
+                feats_g = torch.full((len(paths), 512), float("nan"), dtype=torch.float32, device=device)
+                feats_o = torch.full_like(feats_g, float("nan")) if pairs is not None else None
             for b0 in range(0, len(paths), args.batch_size):
                 bp = paths[b0:b0 + args.batch_size]
                 batch = []
@@ -372,7 +532,8 @@ def main(args, face_provider=None, log=print, cfgs=None):
                     batch.append(u)
                 u8 = torch.from_numpy(np.stack(batch))                       # [b,H,W,3] uint8
                 u8_d = u8.to(device, non_blocking=False)
-                ind, boxes = face_provider(u8.permute(0, 3, 1, 2).float() / 255 * 2 - 1)      # what the reference hands get_face (:637-639)
+                x = u8.permute(0, 3, 1, 2).float() / 255 * 2 - 1      # what the reference hands get_face (:637-639); one object: a detector provider caches by identity
+                ind, boxes = face_provider(x)
                 ind = torch.as_tensor(ind, dtype=torch.bool).cpu()
                 boxes = torch.as_tensor(boxes).to("cpu", torch.int32)
                 boxes = torch.where(ind[:, None], boxes, torch.full_like(boxes, -1)).contiguous()
@@ -387,7 +548,23 @@ def main(args, face_provider=None, log=print, cfgs=None):
                             size_o = u.shape
                         _same_size(u, size_o, path)
                         batch_o.append(u)
-                    sims_p.append(torch.stack(pair_similarity(clip, dino, u8_d, torch.from_numpy(np.stack(batch_o)).to(device))))
+                    u8_o = torch.from_numpy(np.stack(batch_o))
+                    u8_od = u8_o.to(device)
+                    sims_p.append(torch.stack(pair_similarity(clip, dino, u8_d, u8_od)))
+                if face_metrics:
+                    lms = torch.as_tensor(face_provider.landmarks(x)).to("cpu", torch.float32)
+                    lms_p.append(torch.where(ind[:, None, None], lms, torch.full_like(lms, -1.0)))
+                    rows, f = face_features_u8(face_net, u8_d, ind, lms, S_al)
+                    if rows:
+                        feats_g[torch.tensor(rows, device=device) + b0] = f
+                        n_chips += len(rows)
+                    if pairs is not None:          # the original images through the same provider, alignment and network
+                        x_o = u8_o.permute(0, 3, 1, 2).float() / 255 * 2 - 1
+                        ind_o = torch.as_tensor(face_provider(x_o)[0], dtype=torch.bool).cpu()
+                        rows, f = face_features_u8(face_net, u8_od, ind_o, torch.as_tensor(face_provider.landmarks(x_o)).to("cpu", torch.float32), S_al)
+                        if rows:
+                            feats_o[torch.tensor(rows, device=device) + b0] = f
+                            n_chips += len(rows)
                 imgs_d.append(u8_d)
                 ind_p.append(ind)
                 boxes_p.append(boxes)
@@ -408,7 +585,16 @@ def main(args, face_provider=None, log=print, cfgs=None):
             if pairs is not None:
                 sims = torch.cat(sims_p, dim=1).cpu()          # [2, N] fp32: the prompt's one copy
                 semantics[0][prompt_idx], semantics[1][prompt_idx] = sims[0].clone(), sims[1].clone()
+            if pairs is not None or face_metrics:
                 numbers[prompt_idx] = [_image_number(p) for p in paths]
+            if face_metrics:
+                have = ind.nonzero().view(-1).to(device)
+                sim_real = torch.full((len(paths),), float("nan"), dtype=torch.float32, device=device)
+                if len(have):          # one search per prompt
+                    sim_real[have] = nearest_face_similarity(face_db, face_db16, feats_g[have])
+                faces[0][prompt_idx], faces[1][prompt_idx] = torch.cat(lms_p), sim_real.cpu()
+                if pairs is not None:
+                    faces[2][prompt_idx] = (feats_g * feats_o).sum(dim=-1).cpu()          # nan unless both images have a face
             n_images += len(paths)
     with open(os.path.join(args.save_dir, "test_results.pkl"), "wb") as f:
         pickle.dump(results, f)
@@ -422,11 +608,18 @@ def main(args, face_provider=None, log=print, cfgs=None):
             pickle.dump(semantics, f)
         with open(os.path.join(args.save_dir, "semantics.json"), "w") as f:
             json.dump(semantics_summary(semantics, numbers), f, indent=1)
+    if face_metrics:
+        with open(os.path.join(args.save_dir, "faces.pkl"), "wb") as f:
+            pickle.dump(faces, f)
+        with open(os.path.join(args.save_dir, "faces.json"), "w") as f:
+            json.dump(faces_summary(faces, numbers), f, indent=1)
     dt = time.time() - t0
     if log is not None:
         line = {"evaluated_images": n_images, "prompts": len(metrics), "seconds": round(dt, 3), "images_per_s": round(n_images / dt, 2) if dt > 0 else None}
         if pairs is not None:
             line["semantics_pairs"] = n_images
+        if face_metrics:
+            line["face_chips"] = n_chips
         log(json.dumps(line))
     return results, out
 

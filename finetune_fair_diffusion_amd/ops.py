@@ -738,13 +738,25 @@ def patchify_bwd(dpatches, std, N, S, P, scale=1.0, out=None):
     return out
 
 
-def warp_affine(img, src_index, A, S, fill=-1.0):
-    """chips [n,3,S,S] fp16 sampled from img [B,3,H,W] fp16 through the per-chip 2x3 maps A [n,6] (output pixel -> input position)."""
+def warp_affine(img, src_index, A, S, fill=-1.0, mirror=False):
+    """chips [n,3,S,S] fp16 sampled from img [B,3,H,W] fp16 through the per-chip 2x3 maps A [n,6] (output pixel -> input position).  A uint8 img is
+    [B,H,W,3] decoded bytes standing for ``u/255*2-1`` in fp32 (``fd_warp_affine_u8_fwd``, the offline evaluator's path; a ``src_index`` entry outside
+    [0,B) gives a chip of ``fill`` there).  ``mirror``: return (chips, flip(chips, [3])) -- from the bytes both come out of the one launch."""
     n = A.shape[0]
+    if img.dtype == torch.uint8:
+        B, H, W, C = img.shape
+        assert C == 3 and img.is_contiguous(), (img.shape, img.stride())
+        # the entry point cannot see the sizes of the buffers it reads
+        assert src_index.dtype == torch.int32 and tuple(src_index.shape) == (n,) and src_index.is_contiguous() and tuple(A.shape) == (n, 6), (src_index.dtype, src_index.shape, A.shape)
+        chips = torch.empty((n, 3, S, S), dtype=F16, device=img.device)
+        flipped = torch.empty_like(chips) if mirror else None
+        if n > 0:
+            _call("fd_warp_affine_u8_fwd", _p(img), _p(src_index), _p(_chk(A, F32)), fill, _p(chips), _p(flipped), n, B, H, W, S, _stream())
+        return (chips, flipped) if mirror else chips
     _, _, H, W = img.shape
     chips = torch.empty((n, 3, S, S), dtype=F16, device=img.device)
     _call("fd_warp_affine_fwd", _p(_chk(img)), _p(src_index), _p(_chk(A, F32)), fill, _p(chips), n, H, W, S, _stream())
-    return chips
+    return (chips, torch.flip(chips, [3]).contiguous()) if mirror else chips
 
 
 def warp_affine_bwd(dchips, src_index, A, dimg, S):

@@ -362,12 +362,20 @@ int fd_eval_grid_u8(const void* images, const int32_t* order, const int32_t* box
                     uint8_t* grid, int N, int H, int W, int rows, int cols, void* stream);
 
 
-/* ---- offline evaluation of generated images (evaluate_images.py; eval-generated-images.py).  Both entry points read JPEG-decoded uint8 HWC images,
+/* ---- offline evaluation of generated images (evaluate_images.py; eval-generated-images.py).  These entry points read JPEG-decoded uint8 HWC images,
  * a pixel u standing for ((float)u / 255) * 2 - 1 in fp32 (a true division; each operation rounded once).  Additive: FD_ABI_VERSION is unchanged.
  * crop_face (:296-319): crop boxes[b] = x0,y0,x1,y1 (x1, y1 exclusive; may exceed the image -> fill) of img [B,H,W,3] uint8 and resize it bilinearly
  * (align_corners=False, no antialias: the taps and weights of fd_crop_resize_fwd) to chips [B,3,S,S] working dtype NCHW, rounded once at the store.
  * A box with x1 <= x0 or y1 <= y0 (the no-face box -1,-1,-1,-1) gives a chip of ``fill``.  B >= 1; S, H, W 1..4096. */
 int fd_crop_resize_u8_fwd(const uint8_t* img, const int32_t* boxes, float fill, void* chips, int B, int H, int W, int S, void* stream);
+/* image_pipeline (:321-341) from the bytes: the landmark-aligned chips of the face-realism term, fd_warp_affine_fwd with its taps read from img
+ * [B,H,W,3] uint8 as u/255*2-1.  A [n,6] fp32: row-major 2x3 map from output pixel (x,y,1) to the sampling position in input pixels; same bilinear
+ * expression; a tap outside the image reads ``fill``.  chips [n,3,S,S] working dtype NCHW, rounded once at the store; chips_mirror, when not NULL, is a
+ * second buffer of that shape that receives the same values at column S-1-x (flip(chips, [3]), bit for bit: SFNet's second input from the same launch).
+ * src_index [n] int32 on the device selects the image of chip k and is checked ON the device: an entry outside [0,B) gives a chip (and mirror) of
+ * ``fill``.  Refused on the host, nothing launched: null img / src_index / A / chips, n_chips < 1, B < 1, H, W or S outside 1..4096. */
+int fd_warp_affine_u8_fwd(const uint8_t* img, const int32_t* src_index, const float* A, float fill, void* chips, void* chips_mirror, int n_chips, int B,
+                          int H, int W, int S, void* stream);
 /* The whole grid of plot_in_grid_gender_race (:65-168; n_attr = 2) / plot_in_grid_gender_race_age (:171-263; n_attr = 3) in one launch: images
  * [N,H,W,3] uint8 -> grid [rows*(H+20), cols*(W+50*n_attr+20), 3] uint8 (4-byte aligned).  Tile i shows image order[i]: pixels
  * trunc((((u/255)*2-1)*0.5+0.5)*255) (four fp32 roundings); the outline of boxes[order[i]] = x0,y0,x1,y1 (both ends drawn, 4 pixels wide, PIL's rule)
