@@ -2,7 +2,8 @@
 //   G[n, r] += scale * sum_m X[m, n] * T[m, r]        (X,T fp16; G fp32 with arbitrary strides)
 // dUp[N,r]  = dY^T . t   (X = dY, T = t = x.down^T)        dDown[r,K] = u^T . x  (X = x, T = u = dY.up)
 // HBM-bound (reads X once); VALU FMAs, coalesced over n, T rows broadcast.  Two-pass with a fixed
-// reduction order so repeated runs are bit-identical.
+// reduction order so repeated runs are bit-identical.  Batched problems of ranks 17..64 run on the matrix cores instead
+// (lora_wgrad_partial_mfma_multi below).
 #include "common.h"
 
 template <int RP>
@@ -150,6 +151,125 @@ __global__ __launch_bounds__(256) void lora_wgrad_partial_multi(WgradBatch b, fl
     lora_wgrad_partial_vec_body<RP, CV, CGB>(b.X[p], b.ldx[p], b.T[p], b.ldt[p], scratch + b.poff[p], b.M[p], b.N[p], b.rows[p], bx, by, red);
 }
 
+// ---- padded ranks 32 and 64 on the matrix cores.  G^T[r, n] = sum_m T[m, r] X[m, n] is a product whose contraction index is the ROW index of both
+// operands, so both are staged row-major, as they lie in HBM, and their 16x16x32 fragments are read column-wise with ds_read_b64_tr_b16: a 16-lane
+// group g fetches the blocks [4 rows 4g ..][16 columns] and [4 rows 16 + 4g ..][16 columns] of a 32-row stage, lane i supplies the address of row
+// i / 4, columns 4 (i % 4) .. + 3 and receives column i.  A and B take the same k order, so its permutation against the plain operand map cancels.
+// A block of 4 waves owns WG_NC = 320 columns x RP ranks of one row range: wave w the columns 80 w .. + 79 as 5 x RP / 16 accumulator tiles, so X is
+// read from HBM once and T once per 320 columns.  Row strides of 672 B (X) and 160 / 96 B (T) are odd multiples of 32 B: the 8 rows x 32 B that
+// a 32-lane half reads together fall on 8 distinct 32-byte slots of the 256-byte bank row.  Rows past the range are zero in LDS; columns past N
+// are zero too and their results are dropped.  No branch around a transposed read depends on the lane (EXEC is all ones there).
+typedef short fd_s16x4 __attribute__((__vector_size__(8)));
+constexpr int WG_KT = 32, WG_NC = 320, WG_XS = WG_NC + 16;
+
+__device__ __forceinline__ f16x8 wgrad_read_tr(const f16* tile, int stride, int c0, int lane) {
+    const f16* p = tile + (4 * (lane >> 4) + ((lane & 15) >> 2)) * stride + c0 + 4 * (lane & 3);
+    const fd_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fd_s16x4*)p);
+    const fd_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fd_s16x4*)(p + 16 * stride));
+    const f16x4 a = __builtin_bit_cast(f16x4, lo), b = __builtin_bit_cast(f16x4, hi);
+    return (f16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+
+template <int RP>
+__global__ __launch_bounds__(256) void lora_wgrad_partial_mfma_multi(WgradBatch b, float* __restrict__ scratch) {
+    FD_WG_TRACE(21);
+    constexpr int TS = RP + 16, NRT = RP / 16, TCH = RP / 8, XCH = WG_NC / 8, XPT = WG_KT * XCH / 256;
+    static_assert(WG_KT * XCH % 256 == 0 && WG_KT * TCH <= 256, "staging shares of 256 threads");
+    __shared__ __attribute__((aligned(16))) f16 Xs[WG_KT * WG_XS];
+    __shared__ __attribute__((aligned(16))) f16 Ts[WG_KT * TS];
+    int p = 0;
+#pragma unroll 1
+    while (p + 1 < b.n && (int)blockIdx.x >= b.bstart[p + 1]) ++p;
+    const int local = blockIdx.x - b.bstart[p];
+    const int bx = local % b.ncb[p], by = local / b.ncb[p];
+    const f16* __restrict__ X = b.X[p];
+    const f16* __restrict__ T = b.T[p];
+    const int64_t ldx = b.ldx[p], ldt = b.ldt[p];
+    const int N = b.N[p], n0 = bx * WG_NC;
+    const int m0 = by * b.rows[p], m1 = min(m0 + b.rows[p], b.M[p]);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+    f32x4 acc[5][NRT];
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int j = 0; j < NRT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // one stage = 32 rows: 1280 16-byte pieces of X (5 per thread) and 32 * RP / 8 of T (at most one per thread), held in registers across the
+    // MFMAs of the stage before
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    f16x8 xr[XPT], tr = zero8;
+    auto load = [&](int mk) {
+#pragma unroll
+        for (int i = 0; i < XPT; ++i) {
+            const int c = tid + 256 * i, m = mk + c / XCH, col = n0 + (c % XCH) * 8;
+            xr[i] = (m < m1 && col < N) ? *(const f16x8*)(X + (int64_t)m * ldx + col) : zero8;      // N % 8 == 0: a piece is inside or outside
+        }
+        if (tid < WG_KT * TCH) {
+            const int m = mk + tid / TCH;
+            tr = m < m1 ? *(const f16x8*)(T + (int64_t)m * ldt + (tid % TCH) * 8) : zero8;
+        }
+    };
+    load(m0);
+    for (int mk = m0; mk < m1; mk += WG_KT) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < XPT; ++i) {
+            const int c = tid + 256 * i;
+            *(f16x8*)(Xs + (c / XCH) * WG_XS + (c % XCH) * 8) = xr[i];
+        }
+        if (tid < WG_KT * TCH) *(f16x8*)(Ts + (tid / TCH) * TS + (tid % TCH) * 8) = tr;
+        __syncthreads();
+        if (mk + WG_KT < m1) load(mk + WG_KT);
+        f16x8 tf[NRT];
+#pragma unroll
+        for (int j = 0; j < NRT; ++j) tf[j] = wgrad_read_tr(Ts, TS, j * 16, lane);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const f16x8 xf = wgrad_read_tr(Xs, WG_XS, wave * 80 + i * 16, lane);
+#pragma unroll
+            for (int j = 0; j < NRT; ++j) acc[i][j] = FD_MFMA_16x16x32(tf[j], xf, acc[i][j]);
+        }
+    }
+    // C/D map: column (lane & 15) = n, rows 4 (lane >> 4) .. + 3 = four consecutive ranks
+    float* partial = scratch + b.poff[p];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int n = n0 + wave * 80 + i * 16 + (lane & 15);
+        if (n < N) {
+#pragma unroll
+            for (int j = 0; j < NRT; ++j) *(f32x4*)(partial + ((int64_t)by * N + n) * RP + j * 16 + 4 * (lane >> 4)) = acc[i][j];
+        }
+    }
+}
+
+// Final pass of the MFMA arm: one THREAD per (n, padded r), consecutive threads on consecutive floats of a partial row, the splits added in ascending
+// order.  (lora_wgrad_final_multi spends a wave per output element: fine for 320 x 4 outputs, 400 us for the 16 x 1280 x 50 of a rank-50 block.)
+// Here ``ostart`` counts N x RP elements per problem.
+template <int RP>
+__global__ __launch_bounds__(256) void lora_wgrad_final_mfma_multi(WgradBatch b, const float* __restrict__ scratch) {
+    FD_WG_TRACE(22);
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= b.ostart[b.n]) return;
+    int p = 0;
+#pragma unroll 1
+    while (p + 1 < b.n && o >= b.ostart[p + 1]) ++p;
+    const int lo = o - b.ostart[p];
+    const int n = lo / RP, r = lo % RP;
+    if (r >= b.R[p]) return;
+    const int64_t step = (int64_t)b.N[p] * RP;
+    const float* src = scratch + b.poff[p] + lo;
+    float s = 0.f;
+    const int ns = b.nsplit[p];
+    int k = 0;
+    for (; k + 4 <= ns; k += 4) {
+        const float v0 = src[k * step], v1 = src[(k + 1) * step], v2 = src[(k + 2) * step], v3 = src[(k + 3) * step];
+        s = (((s + v0) + v1) + v2) + v3;
+    }
+    for (; k < ns; ++k) s += src[k * step];
+    b.G[p][n * b.sn[p] + r * b.sr[p]] += b.scale[p] * s;
+}
+
 __global__ __launch_bounds__(256) void lora_wgrad_final_multi(WgradBatch b, const float* __restrict__ scratch, int RP) {
     FD_WG_TRACE(19);
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -211,8 +331,62 @@ extern "C" int fd_lora_wgrad(const void* X, int64_t ldx, const void* T, int64_t 
     return fd_check_launch("fd_lora_wgrad");
 }
 
-// Batched weight gradients: ``descs`` is a HOST array of n <= FD_WGRAD_MAX problems that share the padded rank RP (8 or 16) and satisfy the
-// vectorised kernel's alignment (N %% CV == 0, ldx %% CV == 0 with CV = 8 / 4); anything else is rejected (callers fall back to fd_lora_wgrad).
+// The RP = 32 / 64 arm of fd_lora_wgrad_multi (the descriptors' sizes, ranks and counts are already checked).  Splits: about 2 blocks per CU (what the RP = 64 kernel's 172 registers admit) over the
+// whole batch, shared out by work, at least 256 rows each (a split writes and the final pass re-reads N x RP floats: at 256 rows that is as many
+// bytes as the split's X rows, beyond it mostly overhead); halved together until the partials fit the scratch that was passed.
+static int lora_wgrad_multi_mfma(const fd_wgrad_desc* descs, int n, int RP, float* scratch, int64_t scratch_elems, hipStream_t s) {
+    double work = 0;
+    for (int i = 0; i < n; ++i) {
+        const fd_wgrad_desc& d = descs[i];
+        FD_REQUIRE((d.N & 7) == 0, "fd_lora_wgrad_multi: N must be a multiple of 8 for ranks above 16 (problem %d: N=%d)", i, d.N);
+        FD_REQUIRE((d.ldx & 7) == 0 && d.ldx >= d.N, "fd_lora_wgrad_multi: ldx must be a multiple of 8 and >= N for ranks above 16 (problem %d: ldx=%ld)", i, (long)d.ldx);
+        FD_REQUIRE(d.ldt >= RP && (d.ldt & 7) == 0, "fd_lora_wgrad_multi: ldt must be a multiple of 8 and >= %d (problem %d: ldt=%ld)", RP, i, (long)d.ldt);
+        FD_REQUIRE(d.X && ((uintptr_t)d.X & 15) == 0, "fd_lora_wgrad_multi: X must be 16-byte aligned for ranks above 16 (problem %d)", i);
+        FD_REQUIRE(d.T && ((uintptr_t)d.T & 15) == 0, "fd_lora_wgrad_multi: T must be 16-byte aligned for ranks above 16 (problem %d)", i);
+        FD_REQUIRE(d.G, "fd_lora_wgrad_multi: G is null (problem %d)", i);
+        FD_REQUIRE(d.N <= (1 << 20), "fd_lora_wgrad_multi: N must be at most 2^20 for ranks above 16 (problem %d: N=%d)", i, d.N);
+        work += (double)d.M * d.N;
+    }
+    WgradBatch b;
+    b.n = n;
+    int blocks = 0, outs = 0;
+    int64_t poff = 0;
+    for (int div = 1;; div <<= 1) {
+        blocks = 0; outs = 0; poff = 0;
+        bool split = false;
+        for (int i = 0; i < n; ++i) {
+            const fd_wgrad_desc& d = descs[i];
+            const int ncb = (d.N + WG_NC - 1) / WG_NC;
+            int nsplit = (int)(512.0 * ((double)d.M * d.N / work) / ncb + 0.5);
+            if (nsplit > (d.M + 255) / 256) nsplit = (d.M + 255) / 256;
+            nsplit /= div;
+            if (nsplit < 1) nsplit = 1;
+            int rows = (d.M + nsplit - 1) / nsplit;
+            rows = (rows + WG_KT - 1) / WG_KT * WG_KT;
+            nsplit = (d.M + rows - 1) / rows;
+            split |= nsplit > 1;
+            b.X[i] = (const f16*)d.X; b.T[i] = (const f16*)d.T; b.G[i] = d.G;
+            b.ldx[i] = d.ldx; b.ldt[i] = d.ldt; b.sn[i] = d.g_stride_n; b.sr[i] = d.g_stride_r; b.poff[i] = poff;
+            b.M[i] = d.M; b.N[i] = d.N; b.R[i] = d.R; b.rows[i] = rows; b.ncb[i] = ncb; b.nsplit[i] = nsplit; b.scale[i] = d.scale;
+            b.bstart[i] = blocks; b.ostart[i] = outs;
+            blocks += ncb * nsplit;
+            outs += d.N * RP;                      // the final pass of this arm walks whole partial rows
+            poff += (int64_t)nsplit * d.N * RP;
+        }
+        if (poff <= scratch_elems || !split) break;
+    }
+    b.bstart[n] = blocks; b.ostart[n] = outs;
+    FD_REQUIRE(scratch && poff <= scratch_elems, "fd_lora_wgrad_multi: scratch too small (%ld > %ld floats)", (long)poff, (long)scratch_elems);
+    if (RP == 32) hipLaunchKernelGGL(lora_wgrad_partial_mfma_multi<32>, dim3(blocks), dim3(256), 0, s, b, scratch);
+    else hipLaunchKernelGGL(lora_wgrad_partial_mfma_multi<64>, dim3(blocks), dim3(256), 0, s, b, scratch);
+    if (RP == 32) hipLaunchKernelGGL(lora_wgrad_final_mfma_multi<32>, dim3((outs + 255) / 256), dim3(256), 0, s, b, (const float*)scratch);
+    else hipLaunchKernelGGL(lora_wgrad_final_mfma_multi<64>, dim3((outs + 255) / 256), dim3(256), 0, s, b, (const float*)scratch);
+    return fd_check_launch("fd_lora_wgrad_multi");
+}
+
+// Batched weight gradients: ``descs`` is a HOST array of n <= FD_WGRAD_MAX problems that share the padded rank RP (8, 16, 32 or 64).  RP 8 and 16
+// run the vectorised kernel and need its alignment (N %% CV == 0, ldx %% CV == 0 with CV = 8 / 4); RP 32 and 64 run the MFMA kernel and need
+// N %% 8 == 0, ldx %% 8 == 0 and 16-byte aligned X and T; anything else is rejected (callers fall back to fd_lora_wgrad).
 extern "C" int fd_lora_wgrad_multi(const fd_wgrad_desc* descs, int n, float* scratch, int64_t scratch_elems, void* stream) {
     FD_REQUIRE(n >= 1 && n <= FD_WGRAD_MAX, "fd_lora_wgrad_multi: 1..%d problems (got %d)", FD_WGRAD_MAX, n);
     FD_REQUIRE_DESC(descs, fd_wgrad_desc, "fd_lora_wgrad_multi");       // element 0 first: its size is the array stride of the others
@@ -223,10 +397,14 @@ extern "C" int fd_lora_wgrad_multi(const fd_wgrad_desc* descs, int n, float* scr
     double work = 0;
     for (int i = 0; i < n; ++i) {
         const fd_wgrad_desc& d = descs[i];
-        FD_REQUIRE(d.M > 0 && d.N > 0 && d.R > 0 && d.R <= 16, "fd_lora_wgrad_multi: rank must be in 1..16");
-        const int rp = d.R <= 8 ? 8 : 16;
+        FD_REQUIRE(d.M > 0 && d.N > 0 && d.R > 0 && d.R <= 64, "fd_lora_wgrad_multi: rank must be in 1..64 (problem %d: R=%d)", i, d.R);
+        const int rp = d.R <= 8 ? 8 : (d.R <= 16 ? 16 : (d.R <= 32 ? 32 : 64));
         FD_REQUIRE(RP == 0 || rp == RP, "fd_lora_wgrad_multi: mixed padded ranks");
         RP = rp;
+    }
+    if (RP >= 32) return lora_wgrad_multi_mfma(descs, n, RP, scratch, scratch_elems, (hipStream_t)stream);
+    for (int i = 0; i < n; ++i) {
+        const fd_wgrad_desc& d = descs[i];
         const int cv = RP == 8 ? 8 : 4;
         FD_REQUIRE((d.N % cv) == 0 && (d.ldx % cv) == 0 && d.ldt >= RP && (d.ldt & 7) == 0, "fd_lora_wgrad_multi: alignment (N, ldx %% %d; ldt)", cv);
         work += (double)d.M * d.N;

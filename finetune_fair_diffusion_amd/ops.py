@@ -607,12 +607,23 @@ def cross_attn_block(x, ln2, wq, k, vt, L, wo, bo, ln3, heads, rows_per_sample, 
 # ----------------------------------------------------------------------------- LoRA / scheduler / optimizer
 _WGRAD_PENDING = None      # list of (X, T, G, sn, sr, R, scale) while a ``wgrad_batch()`` context is open
 WGRAD_MAX = 16
+WGRAD_MFMA_SCRATCH = 1 << 24   # floats of split partials offered to the rank 17..64 arm of fd_lora_wgrad_multi (64 MiB per stream)
+
+
+def _wgrad_rp(R):
+    return 8 if R <= 8 else 16 if R <= 16 else 32 if R <= 32 else 64
+
+
+def _wgrad_mfma_ok(X, T, R):
+    """What the matrix-core arm of ``fd_lora_wgrad_multi`` (ranks 17..64) asks beyond N and ldx being multiples of 8: T padded to its rank with rows
+    of a multiple of 8 elements, and both operands starting on 16 bytes."""
+    return R <= 64 and T.stride(0) % 8 == 0 and T.stride(0) >= _wgrad_rp(R) and X.data_ptr() % 16 == 0 and T.data_ptr() % 16 == 0
 
 
 def lora_wgrad(X, T, G, sn, sr, R, scale=1.0):
     """G[n*sn + r*sr] += scale * sum_m X[m,n] T[m,r].  Inside ``with wgrad_batch():`` the call is queued and executed with the other
     queued problems in one partial + one final launch when the context closes (the operands are kept alive until then)."""
-    if _WGRAD_PENDING is not None and R <= 16 and X.shape[1] % 8 == 0 and X.stride(0) % 8 == 0:
+    if _WGRAD_PENDING is not None and X.shape[1] % 8 == 0 and X.stride(0) % 8 == 0 and (R <= 16 or _wgrad_mfma_ok(X, T, R)):
         _WGRAD_PENDING.append((X, T, G, sn, sr, R, scale))
         return
     M, N = X.shape
@@ -640,7 +651,7 @@ class wgrad_batch:
 def flush_wgrads(pend):
     by_rp = {}
     for it in pend:
-        by_rp.setdefault(8 if it[5] <= 8 else 16, []).append(it)
+        by_rp.setdefault(8 if it[5] <= 8 else 16 if it[5] <= 16 else _wgrad_rp(it[5]), []).append(it)
     for rp, items in by_rp.items():
         for i in range(0, len(items), WGRAD_MAX):
             chunk = items[i:i + WGRAD_MAX]
@@ -649,7 +660,8 @@ def flush_wgrads(pend):
                 assert X.dtype == F16 and T.dtype == F16 and G.dtype == F32 and X.stride(1) == 1 and T.stride(1) == 1
                 d.X, d.ldx, d.T, d.ldt, d.G = X.data_ptr(), X.stride(0), T.data_ptr(), T.stride(0), G.data_ptr()
                 d.g_stride_n, d.g_stride_r, d.M, d.N, d.R, d.scale = sn, sr, X.shape[0], X.shape[1], R, scale
-            sc = scratch(1 << 22, chunk[0][0].device)
+            # padded ranks 32 / 64: a split's partials are N x RP floats, and 16 problems of the 64 x 64 level want ~500 splits of 320 x 64
+            sc = scratch(1 << 22 if rp <= 16 else WGRAD_MFMA_SCRATCH, chunk[0][0].device)
             _call("fd_lora_wgrad_multi", ctypes.byref(arr), len(chunk), _p(sc), sc.numel(), _stream())
 
 

@@ -247,9 +247,12 @@ int fd_small_attn_bwd(const void* q, const void* k, const void* v, const float* 
 int fd_lora_wgrad(const void* X, int64_t ldx, const void* T, int64_t ldt, float* G, int64_t g_stride_n, int64_t g_stride_r,
                   int M, int N, int R, float scale, float* scratch, int64_t scratch_elems, void* stream);
 
-/* batched form: n <= FD_WGRAD_MAX independent problems (HOST array of descriptors) that share the padded rank (R <= 8, or 9..16) in one
- * partial + one final launch -- the 16 LoRA weight gradients of one transformer block's backward.  Same arithmetic and fixed reduction order
- * per problem as fd_lora_wgrad.  Requires N %% 8 == 0 and ldx %% 8 == 0 (R <= 8) or %% 4 (R <= 16). */
+/* batched form: n <= FD_WGRAD_MAX independent problems (HOST array of descriptors) that share the padded rank (8, 16, 32 or 64: R <= 8, 9..16,
+ * 17..32, 33..64) in one partial + one final launch -- the 16 LoRA weight gradients of one transformer block's backward.  Padded ranks 8 and 16:
+ * same arithmetic and fixed reduction order per problem as fd_lora_wgrad; requires N %% 8 == 0 and ldx %% 8 == 0 (R <= 8) or %% 4 (R <= 16).
+ * Padded ranks 32 and 64: MFMA partial sums (fp32 accumulation of exact 16-bit products) over row splits, the splits added in ascending order, so
+ * repeated calls are bit-identical; requires N %% 8 == 0, ldx %% 8 == 0, ldt >= the padded rank, ldt %% 8 == 0 and X and T aligned to 16 bytes.
+ * A problem that breaks its rule is refused with FD_ERR_ARG before anything is launched (fd_lora_wgrad takes any alignment). */
 #define FD_WGRAD_MAX 16
 typedef struct fd_wgrad_desc {
     int32_t struct_size;                 /* sizeof(fd_wgrad_desc), checked for every element (see fd_gemm_desc) */

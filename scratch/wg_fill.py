@@ -16,7 +16,7 @@ import torch
 from finetune_fair_diffusion_amd import lib, step as step_mod
 
 NAMES = {1: "gemm_glds", 2: "gemm_big", 3: "splitk_reduce", 4: "gemm_skinny", 5: "gemm_pp", 6: "conv_halo", 7: "attn_fwd", 8: "attn_bwd_dq", 9: "attn_bwd_dkdv", 10: "cross_block",
-         11: "gn_reduce", 12: "gn_apply", 13: "gn_bwd_apply", 14: "gn_fused_fwd", 15: "gn_fused_bwd", 16: "layernorm", 17: "geglu_bwd", 18: "lora_wgrad_partial", 19: "lora_wgrad_final", 20: "add"}
+         11: "gn_reduce", 12: "gn_apply", 13: "gn_bwd_apply", 14: "gn_fused_fwd", 15: "gn_fused_bwd", 16: "layernorm", 17: "geglu_bwd", 18: "lora_wgrad_partial", 19: "lora_wgrad_final", 20: "add", 21: "lora_wgrad_partial_mfma", 22: "lora_wgrad_final_mfma"}
 CAP = 110_000_000                     # records (32 bytes each: 3.5 GB)
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
