@@ -20,6 +20,11 @@ cannot be set from YAML and booleans follow Python's ``bool(value)`` -- plus the
                          print each image's index (in the gathered batch) on its tile, as the reference does with Arial Bold (``plot_in_grid``
                          :199-200) -- the number pairs a tile of the ``_ori`` grid with its tile of the ``_generated`` grid.  Not given (default):
                          no index text, the grids as before.  ``--index_font_size`` (default 100, the reference's) is the point size
+  --log_norms            the reference's per-step parameter norms (:2034-2045; exp-2 :2126-2130) in the step's JSON line, for the banks being trained:
+                         ``train_unet_lora_norm`` / ``train_TE_lora_norm`` / ``train_prefix_embedding_norm`` (the mean of the per-tensor L2 norms)
+                         and their ``_ema_norm`` twins, after the step's update, plus ``grad_norm_<bank>``: the global L2 norm of the all-reduced,
+                         averaged gradient the optimiser saw (null when it is not finite).  One device-side reduction per bank and step, read back
+                         asynchronously; off (default): nothing is launched and the line is unchanged
 
 The multi-attribute experiments change a few flags and defaults (exp-3-debias-gender-race/1-main-debias.py:343-660,
 exp-4-debias-gender-race-age/...:343-672, exp-5-...:343-690; exp-2-debias-gender-token/...:453-780 drops the two LoRA switches and adds
@@ -139,7 +144,7 @@ def build_parser(experiment="exp-1"):
 
 
 EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="synthetic", num_classifier_logits=80, lora_up_std=0.0, validation="off",
-                      train_monitor="off", index_font=None, index_font_size=100)
+                      train_monitor="off", index_font=None, index_font_size=100, log_norms=False)
 
 
 def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
@@ -154,6 +159,7 @@ def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
         p.add_argument("--train_monitor", type=str, default="off", choices=["off", "metrics", "plots"])
         p.add_argument("--index_font", type=str, default=None, help="font file, or 'default': print the image index on every grid tile; not given: no text")
         p.add_argument("--index_font_size", type=int, default=100)
+        p.add_argument("--log_norms", action="store_true", default=False, help="log the LoRA / EMA parameter norms and the gradient norm of every step")
     args = p.parse_args(input_args) if input_args is not None else p.parse_args()
     if args.config:
         with open(args.config, "r") as f:

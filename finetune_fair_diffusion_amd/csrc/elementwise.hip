@@ -414,6 +414,114 @@ extern "C" int fd_adamw_ema(float* p, const float* g, float* m, float* v, float*
     return fd_check_launch("fd_adamw_ema");
 }
 
+// ---------------------------------------------------------------- per-tensor norms of the flat banks (fd_bank_norms; header for the contract)
+#define BN_WG 256
+#define BN_BUFS 4
+struct BankBufs { const float* p[BN_BUFS]; };
+static_assert(FD_BANK_NORMS_CH % (4 * BN_WG) == 0, "a full chunk is a whole number of 16-byte loads per thread");// pass 1: chunk c of every present buffer -> partial[b * nchunks + c].  Thread t takes the 16-byte vectors t, t + 256, ... of the chunk (at most
+// CH / 1024 = 8 of them); the up to three elements behind the last vector go to thread 255, which holds at most 7 vectors when there are any (a chunk
+// with a tail has fewer than CH / 4 vectors): no thread sums more than CH / 256 squares.  A chunk whose offset is no multiple of four is read
+// element by element, thread t taking t, t + 256, ...
+__global__ __launch_bounds__(BN_WG) void bank_norms_partial_kernel(BankBufs bufs, int64_t n, const int64_t* table, int nchunks, int nseg, double* partial) {
+    __shared__ double red[BN_WG / 64][BN_BUFS];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int64_t seg = table[3 * (int64_t)c], off = table[3 * (int64_t)c + 1], len64 = table[3 * (int64_t)c + 2];
+    const bool ok = seg >= 0 && seg < nseg && off >= 0 && len64 >= 0 && len64 <= FD_BANK_NORMS_CH && off <= n - len64;
+    const int len = ok ? (int)len64 : 0;
+    float acc[BN_BUFS] = {0.f, 0.f, 0.f, 0.f};
+    if ((off & 3) == 0) {
+        const int nv = len >> 2;
+        for (int v = tid; v < nv; v += BN_WG) {
+#pragma unroll
+            for (int b = 0; b < BN_BUFS; ++b)
+                if (bufs.p[b]) {
+                    const f32x4 x = *(const f32x4*)(bufs.p[b] + off + 4 * (int64_t)v);
+                    acc[b] = fmaf(x[0], x[0], acc[b]);
+                    acc[b] = fmaf(x[1], x[1], acc[b]);
+                    acc[b] = fmaf(x[2], x[2], acc[b]);
+                    acc[b] = fmaf(x[3], x[3], acc[b]);
+                }
+        }
+        if (tid == BN_WG - 1)
+            for (int i = nv << 2; i < len; ++i) {
+#pragma unroll
+                for (int b = 0; b < BN_BUFS; ++b)
+                    if (bufs.p[b]) {
+                        const float x = bufs.p[b][off + i];
+                        acc[b] = fmaf(x, x, acc[b]);
+                    }
+            }
+    } else {
+        for (int i = tid; i < len; i += BN_WG) {
+#pragma unroll
+            for (int b = 0; b < BN_BUFS; ++b)
+                if (bufs.p[b]) {
+                    const float x = bufs.p[b][off + i];
+                    acc[b] = fmaf(x, x, acc[b]);
+                }
+        }
+    }
+    // lanes (xor butterfly: every lane ends with the same sum, whatever the order of two operands), then the four waves in order, all in fp64
+#pragma unroll
+    for (int b = 0; b < BN_BUFS; ++b) {
+        double d = (double)acc[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+        if ((tid & 63) == 0) red[tid >> 6][b] = d;
+    }
+    __syncthreads();
+    if (tid < BN_BUFS && bufs.p[tid]) {
+        double t = red[0][tid];
+        for (int w = 1; w < BN_WG / 64; ++w) t += red[w][tid];
+        partial[(int64_t)tid * nchunks + c] = ok ? t : (double)__builtin_nanf("");
+    }
+}
+// pass 2 (one workgroup): thread t owns segments t, t + 256, ...; then wave b sums up buffer b
+__global__ __launch_bounds__(BN_WG) void bank_norms_finish_kernel(BankBufs bufs, const int64_t* table, int nchunks, int nseg, const double* partial, float* norms,
+                                                                  float* summary) {
+    const int tid = threadIdx.x;
+    for (int s = tid; s < nseg; s += BN_WG) {
+        int lo = 0, hi = nchunks;           // first chunk whose segment is >= s (the table is sorted by segment)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (table[3 * (int64_t)mid] < s) lo = mid + 1; else hi = mid;
+        }
+        int end = lo;
+        while (end < nchunks && table[3 * (int64_t)end] == s) ++end;
+        for (int b = 0; b < BN_BUFS; ++b) {
+            if (!bufs.p[b]) continue;
+            double t = 0.0;
+            for (int c = lo; c < end; ++c) t += partial[(int64_t)b * nchunks + c];
+            norms[(int64_t)b * nseg + s] = (float)sqrt(t);
+        }
+    }
+    __syncthreads();
+    const int b = tid >> 6;
+    if ((tid & 63) == 0 && bufs.p[b]) {
+        double m = 0.0, q = 0.0;
+        for (int s = 0; s < nseg; ++s) m += (double)norms[(int64_t)b * nseg + s];
+        for (int c = 0; c < nchunks; ++c) q += partial[(int64_t)b * nchunks + c];
+        // -ffast-math divides by reciprocal, Newton steps and a residual correction: inf / n would come out as NaN (inf - inf in the residual)
+        summary[2 * b] = isfinite(m) ? (float)(m / (double)nseg) : (float)m;
+        summary[2 * b + 1] = (float)sqrt(q);
+    }
+}
+extern "C" int fd_bank_norms(const float* buf0, const float* buf1, const float* buf2, const float* buf3, int64_t n, const int64_t* table, int nchunks, int nseg,
+                             double* workspace, float* norms, float* summary, void* stream) {
+    BankBufs bufs = {{buf0, buf1, buf2, buf3}};
+    FD_REQUIRE(buf0 || buf1 || buf2 || buf3, "fd_bank_norms: no buffer (at least one of buf0..buf3 must be present)");
+    for (int b = 0; b < BN_BUFS; ++b)
+        FD_REQUIRE(((uintptr_t)bufs.p[b] & 15) == 0, "fd_bank_norms: buf%d is not aligned to 16 bytes", b);
+    FD_REQUIRE(n >= 1 && nchunks >= 1 && nseg >= 1, "fd_bank_norms: n = %lld, nchunks = %d, nseg = %d (supported >= 1 each)", (long long)n, nchunks, nseg);
+    FD_REQUIRE(table && workspace && norms && summary, "fd_bank_norms: null table, workspace, norms or summary");
+    FD_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)norms & 3) == 0 && ((uintptr_t)summary & 3) == 0,
+               "fd_bank_norms: table and workspace must be aligned to 8 bytes, norms and summary to 4");
+    hipLaunchKernelGGL(bank_norms_partial_kernel, dim3((unsigned)nchunks), dim3(BN_WG), 0, (hipStream_t)stream, bufs, n, table, nchunks, nseg, workspace);
+    hipLaunchKernelGGL(bank_norms_finish_kernel, dim3(1), dim3(BN_WG), 0, (hipStream_t)stream, bufs, (const int64_t*)table, nchunks, nseg,
+                       (const double*)workspace, norms, summary);
+    return fd_check_launch("fd_bank_norms");
+}
+
 // ---------------------------------------------------------------- ViT patch embedding input (image regularisers, 1-main-debias.py:1139-1175)
 // chips [N,3,S,S] fp16 NCHW in [-1,1]  ->  patches [N*g*g, Kp] fp16, k = c*P*P + py*P + px (the Conv2d(3,D,P,P) weight order),
 // value ((x+1)/2 - mean_c)/std_c, columns >= 3*P*P zero.

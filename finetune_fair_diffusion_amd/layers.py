@@ -137,6 +137,38 @@ def refresh_pairs(pairs, scale=1.0, ema=False):
     ops._call("fd_lora_refresh_multi", ctypes.byref(arr), len(pairs), ops._stream())
 
 
+NORM_CHUNK = 8192       # FD_BANK_NORMS_CH of include/fairdiff_hip.h: the most elements one workgroup of fd_bank_norms reduces
+NORM_BUFFERS = 4
+
+
+def norm_chunks(extents, ch=NORM_CHUNK):
+    """The chunk table of ``fd_bank_norms`` as a pure host function: ``extents`` = [(offset, number of elements)] per tensor, in bank order ->
+    [(segment, offset, length)], every tensor cut into consecutive ascending pieces of at most ``ch`` elements.  No chunk crosses a tensor or
+    touches the padding between two; an empty tensor gets no chunk (its norm is 0)."""
+    return [(seg, off + at, min(ch, num - at)) for seg, (off, num) in enumerate(extents) for at in range(0, num, ch)]
+
+
+class NormPlan:
+    """What one ``fd_bank_norms`` call over a bank needs besides the buffers, all on the bank's device: the chunk table, the fp64 workspace of the
+    partials and ``out`` (fp32: norms [4, nseg], then (mean, l2) per buffer).  ``extra``: an optional fourth buffer of the bank's layout."""
+
+    def __init__(self, names, extents, numel, dev):
+        chunks = norm_chunks(extents)
+        self.names, self.numel, self.nseg, self.nchunks = list(names), numel, len(extents), len(chunks)
+        self.table = torch.tensor(chunks, dtype=torch.int64).reshape(len(chunks), 3).to(dev)
+        self.workspace = torch.zeros(NORM_BUFFERS * max(self.nchunks, 1), dtype=torch.float64, device=dev)
+        self.out = torch.zeros(NORM_BUFFERS * self.nseg + 2 * NORM_BUFFERS, dtype=F32, device=dev)
+        self.extra = None
+
+    def report(self, host):
+        """``out`` as read back (any float sequence of its length) -> the step's record for this bank; buffers 0, 1, 2 = parameters, EMA, gradient."""
+        ns = self.nseg
+        v = [float(x) for x in host]
+        mean, l2 = (lambda b: v[NORM_BUFFERS * ns + 2 * b]), (lambda b: v[NORM_BUFFERS * ns + 2 * b + 1])
+        return dict(param_mean=mean(0), ema_mean=mean(1), grad_l2=l2(2), param_l2=l2(0), ema_l2=l2(1),
+                    per_tensor={n: (v[s], v[ns + s], v[2 * ns + s]) for s, n in enumerate(self.names)})
+
+
 class ParamBank:
     """Flat fp32 buffer holding named LoRA tensors (+ grad/Adam/EMA twins) so that the gradient
     all-reduce, finite check, AdamW and EMA are each ONE launch over one contiguous buffer
@@ -161,6 +193,13 @@ class ParamBank:
         self.exp_avg = torch.zeros(off, dtype=F32, device=dev)
         self.exp_avg_sq = torch.zeros(off, dtype=F32, device=dev)
         self.ema = torch.zeros(off, dtype=F32, device=dev)
+        self._norm_plan = None
+
+    def norm_plan(self):
+        """The bank's ``NormPlan`` (``ops.adamw_ema(..., norms=)``), built on first use and kept: a trainer that never asks for norms allocates nothing."""
+        if self._norm_plan is None:
+            self._norm_plan = NormPlan(self.names, [self.offsets[n] for n in self.names], self.numel, self.flat.device)
+        return self._norm_plan
 
     def shape(self, n):
         return self._shape[n]

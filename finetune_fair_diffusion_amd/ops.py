@@ -676,8 +676,18 @@ def grad_finite_scale(g, scale, flag):
     _call("fd_grad_finite_scale", _p(_chk(g, F32)), g.numel(), scale, _p(flag), _stream())
 
 
-def adamw_ema(p, g, m, v, ema, lr, b1, b2, eps, wd, step, ema_omd):
-    _call("fd_adamw_ema", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, b1, b2, eps, wd, step, ema_omd, _stream())
+def adamw_ema(p, g, m, v, ema, lr, b1, b2, eps, wd, step, ema_omd, norms=None, apply=True):
+    """AdamW + EMA over the flat buffers of a bank.  ``norms`` (a ``layers.NormPlan`` of the same bank): afterwards, on the same stream, the per-tensor
+    L2 norms of (p, ema, g, norms.extra) -- the state after the update -- land in ``norms.out`` (``fd_bank_norms``; a buffer given as None is left
+    out).  ``apply=False``: the reduction alone, nothing is updated."""
+    if apply:
+        _call("fd_adamw_ema", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, b1, b2, eps, wd, step, ema_omd, _stream())
+    if norms is not None:
+        bufs = (p, ema, g, norms.extra)
+        assert all(t is None or t.numel() == norms.numel for t in bufs), "fd_bank_norms reads the plan's layout: every buffer has the bank's length"
+        bufs = [None if t is None else _p(_chk(t, F32)) for t in bufs]
+        _call("fd_bank_norms", *bufs, norms.numel, _p(norms.table), norms.nchunks, norms.nseg, _p(norms.workspace), _p(norms.out),
+              _p(norms.out[4 * norms.nseg:]), _stream())
 
 
 # ----------------------------------------------------------------------------- classifier pieces

@@ -192,15 +192,18 @@ class FairnessTrainer:
         self.collectives = world_size > 1 or (os.environ.get("FD_FORCE_COLLECTIVES") is not None and dist.is_available() and dist.is_initialized())
         self._hbm_reserve = int(os.environ.get("FD_HBM_RESERVE_MB", "2048")) << 20      # since round 6 also without collectives: the runtime itself needs room (HSA_STATUS_ERROR_OUT_OF_RESOURCES at 0 free)
         self.device = device or unet.device
-        self.banks = []
+        self.banks, self.bank_keys = [], []       # keys: the reference's names in ``train_<key>_norm`` (:2034-2045; exp-2 :2126-2130)
         if getattr(args, "train_unet", False):
             self.banks.append(unet.lora_bank)
+            self.bank_keys.append("unet_lora")
         if getattr(args, "train_text_encoder", False):
             self.banks.append(text_encoder.lora_bank)
+            self.bank_keys.append("TE_lora")
         if self.prefix is not None:
             if self.banks:
                 raise ValueError("exp-2 trains the prefix embedding only (1-main-debias.py:946): no LoRA banks next to it")
             self.banks.append(self.prefix.bank)
+            self.bank_keys.append("prefix_embedding")
         self.ema = [EMAState(args.EMA_decay) for _ in self.banks]
         self.opt_step = 0
         self.lr_step = 0      # lr_scheduler.step() count: advances every step, also when the update is skipped (:2023)
@@ -269,6 +272,11 @@ class FairnessTrainer:
         self.last_monitor = self._mon = None
         # ``evaluation.IndexLabels`` (--index_font; train.py sets it): the index text on the validation grids and the train plots.  None: no text.
         self.index_labels = None
+        # --log_norms (train.py sets it): after every ``sync_and_update`` -- also a skipped one -- ``last_norms`` = {bank key: NormPlan.report}: the
+        # per-tensor L2 norms of parameters, EMA and averaged gradient as they stand after the update, reduced on the device (``fd_bank_norms``)
+        # and read back through one pinned buffer behind an event.  Off: no launch, no table, no buffer; ``last_norms`` stays None.
+        self.log_norms = False
+        self.last_norms = self._norms_host = None
         if self.enumerated_targets:      # the table of the usual global face count (every image has a face); other counts are built on the worker
             composition_table(world_size * getattr(args, "train_images_per_prompt_GPU", 0))
 
@@ -1178,13 +1186,38 @@ class FairnessTrainer:
                                                       getattr(args, "lr_num_cycles", 1), getattr(args, "lr_power", 1.0), args.learning_rate)
         if apply:
             self.lr_step += 1
+        plans = [bank.norm_plan() if self.log_norms else None for bank in self.banks]
         if finite and apply:
             self.opt_step += 1
-            for bank, ema in zip(self.banks, self.ema):
+            for bank, ema, plan in zip(self.banks, self.ema, plans):
                 ops.adamw_ema(bank.flat, bank.grad, bank.exp_avg, bank.exp_avg_sq, bank.ema, self.last_lr, args.adam_beta1,
-                              args.adam_beta2, args.adam_epsilon, args.adam_weight_decay, self.opt_step, ema.next_one_minus_decay())
+                              args.adam_beta2, args.adam_epsilon, args.adam_weight_decay, self.opt_step, ema.next_one_minus_decay(), norms=plan)
+        elif self.log_norms:        # the reference logs the norms whether or not the optimiser stepped (:2034-2045): the reduction alone
+            for bank, plan in zip(self.banks, plans):
+                ops.adamw_ema(bank.flat, bank.grad, bank.exp_avg, bank.exp_avg_sq, bank.ema, self.last_lr, args.adam_beta1,
+                              args.adam_beta2, args.adam_epsilon, args.adam_weight_decay, self.opt_step, 0.0, norms=plan, apply=False)
+        if self.log_norms:
+            ev = self._norms_to_host(plans)
+        if finite and apply:
             if getattr(args, "train_unet", False):
                 self.unet.refresh_lora()
             if getattr(args, "train_text_encoder", False):
                 self.te.refresh_lora()
+        if self.log_norms:          # behind everything this call enqueues: the host waits once, for the copy alone
+            ev.synchronize()
+            sizes = [p.out.numel() for p in plans]
+            parts = self._norms_host.split(sizes)
+            self.last_norms = {k: p.report(h.tolist()) for k, p, h in zip(self.bank_keys, plans, parts)}
         return finite
+
+    def _norms_to_host(self, plans):
+        """Every bank's ``NormPlan.out`` -> one pinned host buffer (kept), non-blocking copies on the current stream; returns the event behind them."""
+        if self._norms_host is None:
+            self._norms_host = torch.empty(sum(p.out.numel() for p in plans), dtype=F32, pin_memory=True)
+        off = 0
+        for p in plans:
+            self._norms_host[off:off + p.out.numel()].copy_(p.out, non_blocking=True)
+            off += p.out.numel()
+        ev = torch.cuda.Event()
+        ev.record()
+        return ev

@@ -20,6 +20,13 @@ device; ``num_faces`` / ``num_faces_total``), ``--train_monitor plots`` also wri
 ``<output_dir>/imgs/train-{global_step}_generated.jpg`` / ``_ori.jpg`` on the steps the reference writes them (``train_plot_number``).
 ``--index_font PATH|default`` prints each image's index on its tile of the validation grids and the train plots, as the reference does with its
 Arial Bold file (``evaluation.IndexLabels``); without it no text is drawn.
+
+``--log_norms`` adds the scalars the reference computes after every optimiser step (:2034-2045; exp-2 :2126-2130) to the step's JSON line, for the
+banks being trained: ``train_unet_lora_norm`` / ``train_unet_lora_ema_norm``, ``train_TE_lora_norm`` / ``train_TE_lora_ema_norm``,
+``train_prefix_embedding_norm`` / ``train_prefix_embedding_ema_norm`` -- ``np.mean`` of the per-tensor L2 norms of the parameters and of their EMA
+after this step's update -- and ``grad_norm_unet_lora`` / ``grad_norm_TE_lora`` / ``grad_norm_prefix_embedding``, the global L2 norm of the
+all-reduced, averaged gradient the optimiser saw (null when it is not finite; the reference parses ``--max_grad_norm`` and never clips, as here).
+They come from one fixed-order reduction per bank on the device (``fd_bank_norms``); without the flag nothing is launched and the line is unchanged.
 """
 import json
 import math
@@ -112,6 +119,15 @@ def train_plot_number(step_in_epoch, global_step, every):
     ``global_step`` as it stands there -- the number of steps completed BEFORE this one (the increment comes after the update, :2250), so the first
     step of a run writes ``train-0_*``.  A resumed run keeps the epoch's own indices (the skipped steps are counted, :1905-1907)."""
     return global_step if every > 0 and step_in_epoch % every == 0 else None
+
+
+def norm_log_fields(last_norms):
+    """``FairnessTrainer.last_norms`` -> the fields of ``--log_norms`` under the reference's names (:2034-2045); a value that is not finite is null."""
+    from .evaluation import _json_safe
+    rec = {}
+    for key, r in last_norms.items():
+        rec.update({f"train_{key}_norm": r["param_mean"], f"train_{key}_ema_norm": r["ema_mean"], f"grad_norm_{key}": r["grad_l2"]})
+    return _json_safe({k: v if math.isfinite(v) else float("nan") for k, v in rec.items()})
 
 
 def load_prompts(args):
@@ -230,6 +246,7 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
     if getattr(args, "index_font", None) and (validation in ("grids", "grids_attrs") or monitor == "plots"):
         from .evaluation import IndexLabels
         trainer.index_labels = IndexLabels(args.index_font, getattr(args, "index_font_size", 100))      # refuses a missing font before the first step
+    trainer.log_norms = bool(getattr(args, "log_norms", False))
 
     def draw_val():
         return evaluation.draw_val_noise(len(prompts_val), args.val_images_per_prompt_GPU, lat)
@@ -301,6 +318,8 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
                     os.makedirs(imgs_dir, exist_ok=True)
                     for tag, grid in mon["grids"].items():          # painted on the device inside the step; encoded here, behind its read-back
                         Image.fromarray(grid.numpy()).save(os.path.join(imgs_dir, f"train-{plot_no}_{tag}.jpg"), quality=25)
+            if trainer.log_norms:
+                rec.update(norm_log_fields(trainer.last_norms))
             (log or print)(json.dumps(rec))
         if evaluation_due(validation, global_step, args.evaluate_every_n_iter):      # :2047-2048
             evaluate(global_step)

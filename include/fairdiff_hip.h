@@ -290,6 +290,25 @@ int fd_cfg_dpm_step(const float* eps, float guidance, float* lat, const float* x
 int fd_grad_finite_scale(float* g, int64_t n, float scale, int32_t* nonfinite_flag, void* stream);
 int fd_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int32_t step, float ema_one_minus_decay, void* stream);
+/* Per-tensor L2 norms of up to four flat fp32 buffers that share one layout (parameters, EMA, gradient, ...: the curves of 1-main-debias.py
+ * :2034-2045, ``np.mean([p.norm().item() for p in ...])``) as a segmented, fixed-order reduction: two launches on ``stream``, no atomics, so two calls
+ * on the same data return the same bits whatever else runs on the device.  Additive: FD_ABI_VERSION is unchanged.
+ * buf0..buf3: device buffers of ``n`` floats each, 16-byte aligned; NULL = absent (at least one is present).  table [nchunks,3] int64 on the device:
+ * (segment, element offset, length) per chunk.  A chunk lies inside one tensor (segment), holds 0..FD_BANK_NORMS_CH elements inside [0, n), and
+ * the table is sorted: segment indices never decrease and the chunks of a segment ascend.  A chunk that breaks the rule is checked ON the device:
+ * nothing of it is read and its partial is NaN.  Elements no chunk covers (the padding between tensors) are never read.
+ * Pass 1, one workgroup of 256 threads per chunk, every present buffer in the same launch: 16-byte loads where the chunk's offset is a multiple of
+ * four elements (plain loads for its last length % 4 elements, and for a whole chunk that starts elsewhere), squares summed per thread in fp32 --
+ * at most FD_BANK_NORMS_CH / 256 of them per thread -- then lanes and waves combined in fp64: workspace[b * nchunks + c] (fp64).
+ * Pass 2, one workgroup: norms[b * nseg + s] = (float)sqrt(sum of segment s's partials in ascending chunk order, fp64); 0 for a segment without
+ * chunks.  summary[2b] = (float)(fp64 mean over s of the fp32 values norms[b, s]), summary[2b + 1] = (float)sqrt(sum of all partials of b in
+ * ascending chunk order).  Rows of an absent buffer are not written.  Inf / NaN stay in the tensor they sit in and in that buffer's summary.
+ * Squares are fp32: |x| >= 2^64 gives inf.  workspace: 4 * nchunks doubles, norms: 4 * nseg floats, summary: 8 floats, all caller-owned.
+ * Refused on the host, nothing launched: no buffer, a buffer not aligned to 16 bytes, n < 1, nchunks < 1, nseg < 1, NULL (or misaligned) table /
+ * workspace / norms / summary. */
+#define FD_BANK_NORMS_CH 8192
+int fd_bank_norms(const float* buf0, const float* buf1, const float* buf2, const float* buf3, int64_t n, const int64_t* table, int nchunks, int nseg,
+                  double* workspace, float* norms, float* summary, void* stream);
 
 /* ---- classifier pieces (torchvision mobilenet_v3_large, 1-main-debias.py:929-935,1369) */
 int fd_dwconv_fwd(const void* x, const float* w /* [k,k,C] */, const float* bias, void* y, int B, int H, int W, int C,
