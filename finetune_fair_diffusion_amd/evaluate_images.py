@@ -48,6 +48,14 @@ An image without a face -- for ``sim_face_ori``: a pair without two faces -- hol
 [N,5,2] / [N] / [N]; landmarks of an image without a face are -1; the third dict is empty without ``--original_imgs_dir``) and ``faces.json``
 (``faces_summary``), and leaves every other file as it is without it.  Weights: ``--opensphere_model_path`` / ``--face_feats_path`` as in training
 (``--synthetic``: ``synthetic_face_state`` / ``synthetic_face_db``).
+
+``--clip_text_score --prompts_path JSON`` (build addition) reports whether the images still show what their prompt asks for (CLIP-T):
+``sim_clip_text[j] = <normalize(image_embeds_j), normalize(text_embeds_i)>`` of the CLIP ViT-H/14 image tower on the ``Resize(224)`` image and the same
+checkpoint's text tower (``text_encoder.CLIPTextModel.text_embeds``, once per prompt) on ``test_prompts[i]`` of the JSON ``generate.py`` read, for
+the folder ``prompt_{i}``; with ``--original_imgs_dir`` the originals are scored against the same text and both scores read the embeddings the pair
+similarity computes, so an image passes the CLIP tower once.  It adds ``text_alignment.pkl`` = ``[sim_text_all, sim_text_ori_all]`` (prompt index ->
+CPU float32 [N] in image order; the second dict is empty without originals) and ``text_alignment.json`` (``text_alignment_summary``), and leaves every
+other file as it is without it.  Weights and tokenizer: ``FD_CLIP_VISION_DIR`` (``--synthetic``: ``synthetic_text_state``, ``train.HashTokenizer``).
 """
 import argparse
 import glob
@@ -73,6 +81,7 @@ DECODE_THREADS = 8                   # fixed: the pool only hides JPEG decoding 
 SYNTHETIC_SEEDS = (9101, 9102, 9103)
 SYNTHETIC_VIT_SEEDS = (21, 22)       # CLIP, DINOv2
 VIT_KEYS = ("clip_vision", "dino")
+SYNTHETIC_TEXT_SEED = 23             # the CLIP text tower of --clip_text_score
 SYNTHETIC_FACE_SEEDS = (9111, 9112)  # SFNet-20, the face database
 FACE_SHORTLIST = 8                   # candidates the fp16 scores hand to the fp32 choice (FairnessTrainer.nearest_face_feats)
 FACE_NET_DEFAULT = "./data/4-opensphere_checkpoints/opensphere_checkpoints/20220424_210641/models/backbone_100000.pth"
@@ -113,6 +122,11 @@ def parse_args(input_args=None):
            "original image's face (faces.pkl, faces.json); not given: no such files")
     a("--opensphere_model_path", type=str, default=argparse.SUPPRESS, help=f"(--face_metrics) SFNet-20 backbone, training's flag; default {FACE_NET_DEFAULT}")
     a("--face_feats_path", type=str, default=argparse.SUPPRESS, help=f"(--face_metrics) face_feats.pkl of real faces, training's flag; default {FACE_DB_DEFAULT}")
+    a("--clip_text_score", action="store_true", default=argparse.SUPPRESS,
+      help="(build addition) CLIP ViT-H/14 cosine similarity of every image to its prompt's text (CLIP-T) and, with --original_imgs_dir, of the original "
+           "images to the same text (text_alignment.pkl, text_alignment.json); needs --prompts_path; not given: no such files")
+    a("--prompts_path", type=str, default=argparse.SUPPRESS,
+      help="(--clip_text_score) the JSON generate.py read: test_prompts[i] is the text of the folder prompt_{i}")
     return p.parse_args(input_args) if input_args is not None else p.parse_args()
 
 
@@ -321,28 +335,145 @@ def pair_similarity(clip, dino, u8_gen, u8_ori):
     uint8 on the device, ``clip`` / ``dino`` the two ``vit.VisionTransformer`` -> (sim_clip [n], sim_dino [n]) fp32 on the device.  Images of one
     size go through each encoder as one batch of 2n; an encoder input size is resized once."""
     n = u8_gen.shape[0]
+    e_clip, e_dino = pair_embeddings(clip, dino, u8_gen, u8_ori)
+    return embedding_similarity(e_clip[:n], e_clip[n:]), embedding_similarity(e_dino[:n], e_dino[n:])
+
+
+def pair_embeddings(clip, dino, u8_gen, u8_ori):
+    """The embeddings ``pair_similarity`` compares: (e_clip [2n,E], e_dino [2n,E']) fp32 on the device, the n generated images' rows first.  With
+    ``--clip_text_score`` the text score reads the CLIP rows too, so that an image passes the CLIP tower once."""
+    n = u8_gen.shape[0]
     assert u8_ori.shape[0] == n and n >= 1, (u8_gen.shape, u8_ori.shape)
     groups = [torch.cat([u8_gen, u8_ori])] if u8_gen.shape == u8_ori.shape else [u8_gen, u8_ori]
-    chips, sims = {}, []
+    chips, embeds = {}, []
     for enc in (clip, dino):
         S = enc.config.image_size
         if S not in chips:
             chips[S] = [_resize_full(u, S) for u in groups]
-        e = torch.cat([enc.forward(c) for c in chips[S]])
-        sims.append(embedding_similarity(e[:n], e[n:]))
-    return sims[0], sims[1]
+        embeds.append(torch.cat([enc.forward(c) for c in chips[S]]))
+    return embeds[0], embeds[1]
+
+
+def _load_encoder(args, cfgs, device, which):
+    """Image encoder ``which`` (0 CLIP, 1 DINOv2) with the weights of the run."""
+    from . import weights as W
+    from .vit import VisionTransformer
+    key = VIT_KEYS[which]
+    if args.synthetic:
+        sd = synthetic_vit_state(which, cfgs)
+    elif which == 0:
+        from .pretrained import load_clip_vision
+        sd = load_clip_vision(os.environ["FD_CLIP_VISION_DIR"], cfgs[key])
+    else:
+        from .pretrained import load_dino
+        sd = load_dino(os.environ["FD_DINO_WEIGHTS"], cfgs[key])
+    mean, std = ((W.CLIP_IMAGE_MEAN, W.CLIP_IMAGE_STD), (W.DINO_IMAGE_MEAN, W.DINO_IMAGE_STD))[which]
+    return VisionTransformer(cfgs[key], sd, device, mean, std)
 
 
 def _load_encoders(args, cfgs, device):
+    return _load_encoder(args, cfgs, device, 0), _load_encoder(args, cfgs, device, 1)
+
+
+# ------------------------------------------------------------------------------------------ text-image alignment (--clip_text_score)
+def synthetic_text_state(cfgs=None):
+    """``--synthetic --clip_text_score``: seeded random weights of the CLIP text tower at the size ``cfgs`` gives it (default: as in ``main``),
+    representable in fp16."""
     from . import weights as W
-    from .vit import VisionTransformer
+    sd = W.synthetic_state_dict(W.clip_param_shapes(_default_cfgs(cfgs)["clip_text_h"]), seed=SYNTHETIC_TEXT_SEED)
+    return {k: v.half().float() for k, v in sd.items()}
+
+
+def load_prompts(path):
+    """``test_prompts`` of the JSON ``generate.py`` reads: ``test_prompts[i]`` is the text of the folder ``prompt_{i}``."""
+    with open(path, "r") as f:
+        prompts = json.load(f)["test_prompts"]
+    if not isinstance(prompts, list) or not all(isinstance(p, str) for p in prompts):
+        raise ValueError(f"--prompts_path {path}: test_prompts must be a list of strings")
+    return prompts
+
+
+def folder_prompts(generated_dir, prompts):
+    """{prompt index: text} of the ``prompt_{i}`` folders of ``generated_dir`` in numeric order; a folder beyond the prompt list is refused."""
+    idx = [_prompt_number(f) for f in _prompt_folders(generated_dir)]
+    beyond = [i for i in idx if not 0 <= i < len(prompts)]
+    if beyond:
+        raise ValueError(f"--prompts_path: the folder prompt_{beyond[0]} has no text, the file holds {len(prompts)} test_prompts "
+                         "(the tree must come from this prompts file)")
+    return {i: prompts[i] for i in idx}
+
+
+def tokenize_prompts(texts, cfg, synthetic, model_dir=None):
+    """Token ids [len(texts), max_position_embeddings] int64 on the host.  Real runs: the checkpoint directory's own ``CLIPTokenizer``, padded to the
+    full length, truncation on (the end-of-text token survives truncation).  ``synthetic``: ``train.HashTokenizer`` on the tower's vocabulary (begin,
+    words, end-of-text = the largest id), padded with id 0."""
+    T = cfg.max_position_embeddings
+    if not texts:
+        return torch.zeros((0, T), dtype=torch.int64)
+    if synthetic:
+        from .train import HashTokenizer
+        tok = HashTokenizer(cfg.vocab_size, max_len=T)
+        ids = torch.zeros((len(texts), T), dtype=torch.int64)
+        for r, text in enumerate(texts):
+            row = tok(text)[0]
+            ids[r, :len(row)] = row
+        return ids
+    from transformers import CLIPTokenizer
+    tok = CLIPTokenizer.from_pretrained(model_dir)
+    return tok(list(texts), return_tensors="pt", padding="max_length", truncation=True, max_length=T).input_ids.to(torch.int64)
+
+
+def _text_inputs(args, cfgs):
+    """Everything ``--clip_text_score`` needs from the host, with its refusals: -> ({prompt index: text}, {prompt index: ids [1,T]}, text tower's state
+    dict).  Nothing here touches the device or ``save_dir``."""
+    path = getattr(args, "prompts_path", None)
+    if path is None:
+        raise ValueError("--clip_text_score needs --prompts_path (the JSON generate.py read: test_prompts[i] is the text of prompt_{i})")
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"--prompts_path {path}: no such file")
+    texts = folder_prompts(args.generated_imgs_dir, load_prompts(path))
+    cfg = cfgs["clip_text_h"]
     if args.synthetic:
-        sds = [synthetic_vit_state(k, cfgs) for k in range(2)]
+        sd, model_dir = synthetic_text_state(cfgs), None
     else:
-        from .pretrained import load_clip_vision, load_dino
-        sds = [load_clip_vision(os.environ["FD_CLIP_VISION_DIR"], cfgs["clip_vision"]), load_dino(os.environ["FD_DINO_WEIGHTS"], cfgs["dino"])]
-    return (VisionTransformer(cfgs["clip_vision"], sds[0], device, W.CLIP_IMAGE_MEAN, W.CLIP_IMAGE_STD),
-            VisionTransformer(cfgs["dino"], sds[1], device, W.DINO_IMAGE_MEAN, W.DINO_IMAGE_STD))
+        model_dir = os.environ.get("FD_CLIP_VISION_DIR")
+        if not model_dir:
+            raise FileNotFoundError("--clip_text_score needs FD_CLIP_VISION_DIR (CLIP ViT-H/14 directory: its checkpoint carries the text tower and its "
+                                    "tokenizer files; pass --synthetic for synthetic weights)")
+        from .pretrained import load_clip_text
+        sd = load_clip_text(model_dir, cfg)          # KeyError on a checkpoint without the text tower
+    ids = tokenize_prompts(list(texts.values()), cfg, args.synthetic, model_dir)
+    return texts, {i: ids[r:r + 1] for r, i in enumerate(texts)}, sd
+
+
+def text_alignment(clip_vision, clip_text, u8, input_ids):
+    """CLIP-T of decoded images: u8 [n,H,W,3] uint8 on the device, input_ids [1,T] (one text for all images) or [n,T] int64 on the host ->
+    ``<normalize(image_embeds), normalize(text_embeds)>`` [n] fp32 on the device.  The image side is ``pair_similarity``'s: ``Resize`` from the bytes,
+    then the CLIP image tower; the text side is ``CLIPTextModel.text_embeds``."""
+    e = clip_vision.forward(_resize_full(u8, clip_vision.config.image_size))
+    return embedding_similarity(e, clip_text.text_embeds(input_ids))
+
+
+def text_alignment_summary(sims, image_numbers_by_prompt, texts):
+    """The content of ``text_alignment.json`` from the content of ``text_alignment.pkl``: ``sims`` = [sim_text_all, sim_text_ori_all] ({prompt index:
+    [N] similarities in image order}; the second dict empty without ``--original_imgs_dir``), ``image_numbers_by_prompt`` = {prompt index: the N
+    numbers ``j`` of ``img_j.jpg``}, ``texts`` = {prompt index: text}.  ``argmin_clip_t`` is the image NUMBER of the least aligned image (the first one
+    on a tie); ``clip_t_delta = clip_t - clip_t_ori``; ``mean`` is the mean over prompts of the per-prompt means, as in ``metrics.json``."""
+    sim_all, ori_all = sims
+    per = {}
+    for i, numbers in image_numbers_by_prompt.items():
+        s = np.asarray(sim_all[i], dtype=np.float64).reshape(-1)
+        assert len(s) == len(numbers) and len(s) > 0, (i, len(s), len(numbers))
+        row = {"prompt": texts[i], "clip_t": float(s.mean()), "min_clip_t": float(s.min()), "argmin_clip_t": int(numbers[int(s.argmin())])}
+        if ori_all:
+            o = np.asarray(ori_all[i], dtype=np.float64).reshape(-1)
+            assert len(o) == len(numbers), (i, len(o), len(numbers))
+            row["clip_t_ori"] = float(o.mean())
+            row["clip_t_delta"] = row["clip_t"] - row["clip_t_ori"]
+        per[str(i)] = row
+    keys = (("clip_t", "clip_t_ori", "clip_t_delta") if ori_all else ("clip_t",)) if per else ()
+    mean = {k: float(np.array([m[k] for m in per.values()]).mean()) for k in keys}
+    return _json_safe({"per_prompt": per, "mean": mean})
 
 
 # ------------------------------------------------------------------------------------------ face realism and identity (--face_metrics)
@@ -459,6 +590,9 @@ def main(args, face_provider=None, log=print, cfgs=None):
     face_metrics = bool(getattr(args, "face_metrics", False))
     if face_metrics and not args.synthetic:          # refused before any device work and before anything is written
         _face_weight_paths(args)
+    text_score = bool(getattr(args, "clip_text_score", False))
+    if text_score:          # its refusals are host work: before any device work and before anything is written
+        texts, text_ids, text_sd = _text_inputs(args, _default_cfgs(cfgs))
     if not torch.cuda.is_available():
         raise RuntimeError("finetune_fair_diffusion_amd.evaluate_images needs an MI355X (HIP device); there is no CPU path")
     original_dir = getattr(args, "original_imgs_dir", None)
@@ -493,6 +627,12 @@ def main(args, face_provider=None, log=print, cfgs=None):
             sd = load_classifier(path, ATTR_K[which])
         classifiers.append(MobileNetV3Large(sd, device, ATTR_K[which]))
     clip, dino = _load_encoders(args, _default_cfgs(cfgs), device) if pairs is not None else (None, None)
+    if text_score:
+        from .text_encoder import CLIPTextModel
+        if clip is None:
+            clip = _load_encoder(args, _default_cfgs(cfgs), device, 0)
+        clip_text = CLIPTextModel(_default_cfgs(cfgs)["clip_text_h"], text_sd, device)
+        del text_sd
     face_net, face_db, face_db16 = _load_face_models(args, device) if face_metrics else (None, None, None)
 
     labels = IndexLabels(args.index_font, getattr(args, "index_font_size", LABEL_FONT_SIZE)) if getattr(args, "index_font", None) and args.grid != "off" else None
@@ -501,6 +641,7 @@ def main(args, face_provider=None, log=print, cfgs=None):
     results = [{}, {}, {}, {}, {}]          # indicators, boxes, gender / race / age logits
     metrics = {}
     semantics, numbers = [{}, {}], {}       # CLIP / DINOv2 similarities and the image numbers they belong to (--original_imgs_dir)
+    text_sims = [{}, {}]                    # CLIP similarity to the prompt's text of the generated and of the original images (--clip_text_score)
     faces, n_chips = [{}, {}, {}], 0        # landmarks, similarity to the nearest real face, to the original's face (--face_metrics)
     S_al = args.size_aligned_face
     n_images, t0 = 0, time.time()
@@ -517,6 +658,8 @@ def main(args, face_provider=None, log=print, cfgs=None):
                 paths_o = [o for _, o in pairs[prompt_idx]]
                 assert [g for g, _ in pairs[prompt_idx]] == paths, (prompt_idx, "the generated tree changed after it was paired")
                 decoded_o, size_o, sims_p = pool.map(_decode, paths_o), None, []
+            if text_score:          # the text tower runs once per prompt
+                e_text, tsims_p = clip_text.text_embeds(text_ids[prompt_idx]).float(), []
             if face_metrics:          # per prompt: unit features [N,512] of the generated and the original faces, nan rows where there is none
                 lms_p = []
                 feats_g = torch.full((len(paths), 512), float("nan"), dtype=torch.float32, device=device)
@@ -550,7 +693,13 @@ def main(args, face_provider=None, log=print, cfgs=None):
                         batch_o.append(u)
                     u8_o = torch.from_numpy(np.stack(batch_o))
                     u8_od = u8_o.to(device)
-                    sims_p.append(torch.stack(pair_similarity(clip, dino, u8_d, u8_od)))
+                    e_clip, e_dino = pair_embeddings(clip, dino, u8_d, u8_od)          # generated rows, then the originals'
+                    b = len(bp)
+                    sims_p.append(torch.stack([embedding_similarity(e_clip[:b], e_clip[b:]), embedding_similarity(e_dino[:b], e_dino[b:])]))
+                    if text_score:          # the embeddings the pair similarity just used: each image passes the CLIP tower once
+                        tsims_p.append(torch.stack([embedding_similarity(e_clip[:b], e_text), embedding_similarity(e_clip[b:], e_text)]))
+                elif text_score:
+                    tsims_p.append(embedding_similarity(clip.forward(_resize_full(u8_d, clip.config.image_size)), e_text)[None])
                 if face_metrics:
                     lms = torch.as_tensor(face_provider.landmarks(x)).to("cpu", torch.float32)
                     lms_p.append(torch.where(ind[:, None, None], lms, torch.full_like(lms, -1.0)))
@@ -585,7 +734,12 @@ def main(args, face_provider=None, log=print, cfgs=None):
             if pairs is not None:
                 sims = torch.cat(sims_p, dim=1).cpu()          # [2, N] fp32: the prompt's one copy
                 semantics[0][prompt_idx], semantics[1][prompt_idx] = sims[0].clone(), sims[1].clone()
-            if pairs is not None or face_metrics:
+            if text_score:
+                tsims = torch.cat(tsims_p, dim=1).cpu()          # [1 or 2, N] fp32: the prompt's one copy
+                text_sims[0][prompt_idx] = tsims[0].clone()
+                if pairs is not None:
+                    text_sims[1][prompt_idx] = tsims[1].clone()
+            if pairs is not None or face_metrics or text_score:
                 numbers[prompt_idx] = [_image_number(p) for p in paths]
             if face_metrics:
                 have = ind.nonzero().view(-1).to(device)
@@ -613,6 +767,11 @@ def main(args, face_provider=None, log=print, cfgs=None):
             pickle.dump(faces, f)
         with open(os.path.join(args.save_dir, "faces.json"), "w") as f:
             json.dump(faces_summary(faces, numbers), f, indent=1)
+    if text_score:
+        with open(os.path.join(args.save_dir, "text_alignment.pkl"), "wb") as f:
+            pickle.dump(text_sims, f)
+        with open(os.path.join(args.save_dir, "text_alignment.json"), "w") as f:
+            json.dump(text_alignment_summary(text_sims, numbers, texts), f, indent=1)
     dt = time.time() - t0
     if log is not None:
         line = {"evaluated_images": n_images, "prompts": len(metrics), "seconds": round(dt, 3), "images_per_s": round(n_images / dt, 2) if dt > 0 else None}
@@ -620,6 +779,8 @@ def main(args, face_provider=None, log=print, cfgs=None):
             line["semantics_pairs"] = n_images
         if face_metrics:
             line["face_chips"] = n_chips
+        if text_score:
+            line["text_prompts"] = len(text_sims[0])
         log(json.dumps(line))
     return results, out
 

@@ -14,14 +14,18 @@ from .text_encoder import CLIPTextModel
 from .unet import UNet2DConditionModel
 from .vae import AutoencoderKL
 
-SD15 = dict(unet=W.UNetConfig(), vae=W.VAEConfig(), clip=W.CLIPTextConfig(), clip_vision=W.CLIP_VIT_H14, dino=W.DINOV2_VITB14)
+SD15 = dict(unet=W.UNetConfig(), vae=W.VAEConfig(), clip=W.CLIPTextConfig(), clip_vision=W.CLIP_VIT_H14, dino=W.DINOV2_VITB14,
+            clip_text_h=W.CLIP_VIT_H14_TEXT)
 TINY = dict(unet=W.UNetConfig(block_out_channels=(64, 128, 256, 256), attention_head_dim=4, cross_attention_dim=64, sample_size=32),
             vae=W.VAEConfig(block_out_channels=(32, 64, 64, 64)),
             clip=W.CLIPTextConfig(vocab_size=1000, hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2),
             clip_vision=W.ViTConfig(kind="clip", image_size=56, hidden_size=160, num_hidden_layers=2, num_attention_heads=2, intermediate_size=320,
                                     projection_dim=48, pos_grid=4),
             dino=W.ViTConfig(kind="dino", image_size=56, hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256,
-                             projection_dim=0, layer_norm_eps=1e-6, pos_grid=6))
+                             projection_dim=0, layer_norm_eps=1e-6, pos_grid=6),
+            # head dim 64 as in the real ViT-H text tower; the projection width is clip_vision's
+            clip_text_h=W.CLIPTextConfig(vocab_size=1000, hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2,
+                                         hidden_act="gelu", projection_dim=48))
 
 
 def synthetic_tokens(L=13, vocab=49408, seed=1):

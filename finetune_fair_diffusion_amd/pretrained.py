@@ -109,10 +109,22 @@ def load_face_db(path):
 
 def load_clip_vision(model_dir, cfg):
     """A local ``CLIPVisionModelWithProjection`` directory (the hub snapshot of laion/CLIP-ViT-H-14-laion2B-s32B-b79K, :948-951);
-    full CLIP checkpoints carry the text tower too, which the key filter drops."""
+    full CLIP checkpoints carry the text tower too, which the key filter drops (``load_clip_text`` keeps it)."""
     sd = _read([os.path.join(model_dir, "model.safetensors"), os.path.join(model_dir, "pytorch_model.bin"),
                 os.path.join(model_dir, "open_clip_pytorch_model.bin")])
     return _select(sd, W.vit_param_shapes(cfg), "clip_vision")
+
+
+def load_clip_text(model_dir, cfg):
+    """The text tower of the directory ``load_clip_vision`` reads (a full ``CLIPModel`` checkpoint): the ``text_model.*`` keys and
+    ``text_projection.weight``.  A vision-only checkpoint raises a KeyError that names the first missing key."""
+    sd = _read([os.path.join(model_dir, "model.safetensors"), os.path.join(model_dir, "pytorch_model.bin"),
+                os.path.join(model_dir, "open_clip_pytorch_model.bin")])
+    shapes = W.clip_param_shapes(cfg)
+    missing = [k for k in shapes if k not in sd]
+    if missing:
+        raise KeyError(f"clip_text: {model_dir} has no text tower: {missing[0]} is missing ({len(missing)} of {len(shapes)} tensors)")
+    return _select(sd, shapes, "clip_text")
 
 
 def load_dino(path, cfg):

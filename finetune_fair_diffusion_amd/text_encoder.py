@@ -32,6 +32,7 @@ class CLIPTextModel:
                 v=Linear(sd, p + "self_attn.v_proj", dev), o=Linear(sd, p + "self_attn.out_proj", dev),
                 fc1=Linear(sd, p + "mlp.fc1", dev), fc2=Linear(sd, p + "mlp.fc2", dev), lora={}))
         self.final_ln = Norm(sd, "text_model.final_layer_norm", dev)
+        self.text_proj = sd["text_projection.weight"].to(dev, F16).contiguous() if cfg.projection_dim > 0 else None
         self.lora_bank = None
         self._ctx = None
 
@@ -69,6 +70,7 @@ class CLIPTextModel:
         B, T = input_ids.shape
         D, H = cfg.hidden_size, cfg.num_attention_heads
         d = D // H
+        act = cfg.hidden_act
         vocab = self.tok.shape[0]
         oov = input_ids >= vocab            # host tensor (token ids arrive from the tokenizer on the CPU): no device sync
         if prefix is not None:
@@ -103,9 +105,9 @@ class CLIPTextModel:
             n2, s2 = ops.layernorm(h1, L["ln2"].gamma, L["ln2"].beta, cfg.layer_norm_eps, save_stats=True)
             if record:
                 z, t1 = lora_linear_fwd(n2, L["fc1"], lo.get("fc1"))
-                m = ops.act_fwd(z, "quick_gelu")
+                m = ops.act_fwd(z, act)
             else:
-                m, t1 = lora_linear_fwd(n2, L["fc1"], lo.get("fc1"), act="quick_gelu")
+                m, t1 = lora_linear_fwd(n2, L["fc1"], lo.get("fc1"), act=act)
                 z = None
             h2, t2 = lora_linear_fwd(m, L["fc2"], lo.get("fc2"), residual=h1)
             if record:
@@ -118,6 +120,18 @@ class CLIPTextModel:
 
     __call__ = forward
 
+    def text_embeds(self, input_ids):
+        """``CLIPTextModelWithProjection(input_ids).text_embeds``: input_ids [B,T] int64 on the host -> [B, projection_dim] in the working dtype.
+        The final-LayerNorm row at the first position holding the row's largest id (the end-of-text id is the largest of CLIP's vocabulary)
+        times ``text_projection``.  No key mask: under the causal mask nothing behind that position reaches it, padding included."""
+        if self.text_proj is None:
+            raise ValueError("CLIPTextModel.text_embeds: this tower has no text_projection (config.projection_dim is 0)")
+        B, T = input_ids.shape
+        y = self.forward(input_ids)[0]
+        rows = torch.arange(B) * T + input_ids.argmax(dim=-1)            # host ids: argmax returns the first maximum
+        pooled = y.view(B * T, -1)[rows.to(self.device)].contiguous()          # device gather: plumbing, like the embedding gather
+        return ops.gemm(pooled, self.text_proj)
+
     def backward(self, d_out, gscale):
         """d_out: [B,T,D] fp16 = gscale * dL/d(last_hidden_state).  Accumulates the LoRA gradients; returns gscale * dL/d(input embeddings)
         [B,T,D] fp16 (token + position embedding sum: what exp-2's prefix vectors enter through)."""
@@ -129,7 +143,7 @@ class CLIPTextModel:
         for L, s in zip(reversed(self.layers), reversed(c["layers"])):
             lo = L["lora"]
             dm = lora_linear_bwd(dx, s["m"], s["t2"], L["fc2"], lo.get("fc2"), gscale)
-            dz = ops.act_bwd(s["z"], dm, "quick_gelu")
+            dz = ops.act_bwd(s["z"], dm, cfg.hidden_act)
             dn2 = lora_linear_bwd(dz, s["n2"], s["t1"], L["fc1"], lo.get("fc1"), gscale)
             dh1 = ops.layernorm_bwd(s["h1"], dn2, L["ln2"].gamma, s["s2"], add=dx)
             da = lora_linear_bwd(dh1, s["a"], s["to"], L["o"], lo.get("o"), gscale)

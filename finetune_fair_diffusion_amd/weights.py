@@ -46,6 +46,8 @@ class CLIPTextConfig:
     num_attention_heads: int = 12
     max_position_embeddings: int = 77
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"       # "gelu" (exact): the ViT-H/14 text tower
+    projection_dim: int = 0              # > 0: ``text_projection`` on the end-of-text row (CLIPTextModelWithProjection)
 
 
 # ------------------------------------------------------------------------------------------ U-Net
@@ -203,7 +205,14 @@ def clip_param_shapes(cfg: CLIPTextConfig) -> "OrderedDict[str, tuple]":
         sd[p + "mlp.fc2.weight"] = (D, I); sd[p + "mlp.fc2.bias"] = (D,)
         sd[p + "layer_norm2.weight"] = (D,); sd[p + "layer_norm2.bias"] = (D,)
     sd["text_model.final_layer_norm.weight"] = (D,); sd["text_model.final_layer_norm.bias"] = (D,)
+    if cfg.projection_dim > 0:
+        sd["text_projection.weight"] = (cfg.projection_dim, D)          # no bias
     return sd
+
+
+# text tower of laion/CLIP-ViT-H-14 (the checkpoint of ``CLIP_VIT_H14`` below): 354,032,640 parameters
+CLIP_VIT_H14_TEXT = CLIPTextConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, hidden_act="gelu",
+                                   projection_dim=1024)
 
 
 def clip_lora_param_shapes(cfg: CLIPTextConfig, rank: int) -> "OrderedDict[str, tuple]":
