@@ -485,4 +485,109 @@ extern "C" int fd_lora_refresh_multi(const fd_lora_refresh_desc* descs, int n, v
     return fd_check_launch("fd_lora_refresh_multi");
 }
 
+
+// ------------------------------------------------------------------ folding LoRA pairs into their base weights (fd_lora_merge_multi; header for the contract)
+// out[n, k] = base[n, k] + scale * sum_j up[n, j] * down[j, k], all fp32, j ascending in one fma chain per element: plain VALU, no atomics, no MFMA, so
+// the bits depend on the inputs alone.  One workgroup of 256 threads per 32 x 64 tile of out: the tile's 32 rows of up (contiguous in memory) and its
+// 64 columns of down are staged in LDS once (25 KB), lane c of wave g then owns column c of the rows 8g .. 8g + 7 -- the down value is one LDS read per j
+// shared by eight fmas; the up tile is kept TRANSPOSED ([j][row], row stride 36 floats: 16-byte aligned rows, and the 32 consecutive j of a coalesced
+// staging read land on 16 banks instead of one), so the eight up values of a j are two 16-byte wave-wide broadcast reads (one 4-byte read each made the
+// loop LDS-issue-bound: 9 LDS reads per 8 fmas).  base is read once and out written once, a 256-byte row segment per wave and row; every GLOBAL access is
+// a 4-byte one, because down and up are views into a flat bank of which only that alignment is known.
+#define FD_MERGE_MAX 16
+#define FD_MERGE_TN 32
+#define FD_MERGE_TK 64
+#define FD_MERGE_RMAX 64
+#define FD_MERGE_UP_LD 36
+struct MergeBatch { fd_lora_merge_desc d[FD_MERGE_MAX]; int tstart[FD_MERGE_MAX + 1]; int n; };
+
+__global__ __launch_bounds__(256) void lora_merge_kernel(MergeBatch b) {
+    __shared__ __attribute__((aligned(16))) float s_up[FD_MERGE_RMAX * FD_MERGE_UP_LD];
+    __shared__ float s_dn[FD_MERGE_RMAX * FD_MERGE_TK];
+    int i = 0;
+    while (i + 1 < b.n && (int)blockIdx.x >= b.tstart[i + 1]) ++i;
+    const fd_lora_merge_desc& p = b.d[i];
+    const int t = (int)blockIdx.x - b.tstart[i];
+    const int tk = (p.K + FD_MERGE_TK - 1) / FD_MERGE_TK;
+    const int n0 = (t / tk) * FD_MERGE_TN, k0 = (t % tk) * FD_MERGE_TK;
+    const int r = p.r;
+    const int rows = p.N - n0 < FD_MERGE_TN ? p.N - n0 : FD_MERGE_TN;
+    const float* up = p.up + (int64_t)n0 * r;
+    for (int e = threadIdx.x; e < FD_MERGE_TN * r; e += 256) {
+        const int row = e / r, j = e - row * r;
+        s_up[j * FD_MERGE_UP_LD + row] = e < rows * r ? up[e] : 0.f;
+    }
+    const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int k = k0 + c;
+    for (int j = g; j < r; j += 4) s_dn[j * FD_MERGE_TK + c] = k < p.K ? p.down[(int64_t)j * p.K + k] : 0.f;
+    __syncthreads();
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+    for (int j = 0; j < r; ++j) {
+        const float d = s_dn[j * FD_MERGE_TK + c];
+        const float4 u0 = *(const float4*)(s_up + j * FD_MERGE_UP_LD + g * 8), u1 = *(const float4*)(s_up + j * FD_MERGE_UP_LD + g * 8 + 4);
+        acc[0] = fmaf(u0.x, d, acc[0]); acc[1] = fmaf(u0.y, d, acc[1]); acc[2] = fmaf(u0.z, d, acc[2]); acc[3] = fmaf(u0.w, d, acc[3]);
+        acc[4] = fmaf(u1.x, d, acc[4]); acc[5] = fmaf(u1.y, d, acc[5]); acc[6] = fmaf(u1.z, d, acc[6]); acc[7] = fmaf(u1.w, d, acc[7]);
+    }
+    if (k >= p.K) return;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int n = n0 + g * 8 + q;
+        if (n < p.N) {
+            const int64_t at = (int64_t)n * p.K + k;
+            p.out[at] = fmaf(p.scale, acc[q], p.base[at]);      // the same thread reads base[at] and writes out[at]: out == base is safe
+        }
+    }
+}
+
+static inline bool merge_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
+    return na > 0 && nb > 0 && (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+extern "C" int fd_lora_merge_multi(const fd_lora_merge_desc* descs, int n, void* stream) {
+    FD_REQUIRE(descs && n > 0, "fd_lora_merge_multi: no pairs");
+    for (int i = 0; i < n; ++i) FD_REQUIRE_DESC(descs + i, fd_lora_merge_desc, "fd_lora_merge_multi");
+    // everything is refused here, before the first launch
+    for (int i = 0; i < n; ++i) {
+        const fd_lora_merge_desc& p = descs[i];
+        FD_REQUIRE(p.down && p.up && p.base && p.out, "fd_lora_merge_multi: null down, up, base or out (pair %d)", i);
+        FD_REQUIRE((((uintptr_t)p.down | (uintptr_t)p.up | (uintptr_t)p.base | (uintptr_t)p.out) & 3) == 0, "fd_lora_merge_multi: a pointer of pair %d is not aligned to 4 bytes", i);
+        FD_REQUIRE(p.r >= 1 && p.r <= FD_MERGE_RMAX, "fd_lora_merge_multi: rank must be in 1..64 (pair %d: r = %d)", i, p.r);
+        FD_REQUIRE(p.N >= 0 && p.K >= 0 && p.N <= 0x7fffff00 && p.K <= 0x7fffff00, "fd_lora_merge_multi: negative or oversized extent (pair %d: N = %d, K = %d)", i, p.N, p.K);
+    }
+    for (int i = 0; i < n; ++i) {
+        const fd_lora_merge_desc& p = descs[i];
+        const int64_t no = (int64_t)p.N * p.K;
+        for (int j = 0; j < n; ++j) {
+            const fd_lora_merge_desc& q = descs[j];
+            const int64_t nq = (int64_t)q.N * q.K;
+            const bool in_place = i == j && p.out == p.base;
+            FD_REQUIRE(in_place || !merge_overlap(p.out, no, q.base, nq), "fd_lora_merge_multi: out of pair %d overlaps base of pair %d (only out == base of one pair is allowed)", i, j);
+            FD_REQUIRE(i == j || !merge_overlap(p.out, no, q.out, nq), "fd_lora_merge_multi: out of pair %d overlaps out of pair %d", i, j);
+            FD_REQUIRE(!merge_overlap(p.out, no, q.down, (int64_t)q.r * q.K) && !merge_overlap(p.out, no, q.up, (int64_t)q.N * q.r),
+                       "fd_lora_merge_multi: out of pair %d overlaps down or up of pair %d", i, j);
+        }
+    }
+    for (int i0 = 0; i0 < n; i0 += FD_MERGE_MAX) {
+        int64_t tiles = 0;
+        for (int i = i0; i < n && i < i0 + FD_MERGE_MAX; ++i)
+            tiles += (int64_t)((descs[i].N + FD_MERGE_TN - 1) / FD_MERGE_TN) * ((descs[i].K + FD_MERGE_TK - 1) / FD_MERGE_TK);
+        FD_REQUIRE(tiles <= 0x7fffffff, "fd_lora_merge_multi: pairs %d.. hold %lld tiles of 32 x 64 (one launch takes 2^31 - 1)", i0, (long long)tiles);
+    }
+    for (int i0 = 0; i0 < n; i0 += FD_MERGE_MAX) {
+        MergeBatch b;
+        b.n = n - i0 < FD_MERGE_MAX ? n - i0 : FD_MERGE_MAX;
+        int tiles = 0;
+        for (int i = 0; i < FD_MERGE_MAX; ++i) {
+            b.d[i] = descs[i0 + (i < b.n ? i : 0)];
+            b.tstart[i] = tiles;
+            if (i < b.n) tiles += ((b.d[i].N + FD_MERGE_TN - 1) / FD_MERGE_TN) * ((b.d[i].K + FD_MERGE_TK - 1) / FD_MERGE_TK);
+        }
+        b.tstart[FD_MERGE_MAX] = tiles;
+        if (tiles > 0) hipLaunchKernelGGL(lora_merge_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, b);
+    }
+    return fd_check_launch("fd_lora_merge_multi");
+}
+
 FD_WGT_SETTER(lora)

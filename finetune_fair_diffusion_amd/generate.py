@@ -9,6 +9,8 @@ in the reference, as here, depends on PYTHONHASHSEED), same skip-existing-files 
 ``save_dir/prompt_{i}/img_{j}.jpg``.  ``--load_prefix_embedding_from`` (exp-2's learned prefix tokens, gen-images.py:272-343, :523-538): the
 ``number_prefix_tokens`` placeholder tokens are prepended to every prompt and their embeddings replaced by the loaded ones
 (``prefix_tokens`` / ``generate_image(..., prefix=)``); the uncond branch follows ``StableDiffusionPipeline._encode_prompt`` (no padding mask).
+``--merge_lora`` (build addition, off by default): the loaded LoRA files are folded into the base weights in fp32 (``merge.merge_state_dict``) before the
+models are built, which then carry no LoRA at all -- the images of a directory written by ``python -m finetune_fair_diffusion_amd.merge``, byte for byte.
 """
 import argparse
 import json
@@ -40,6 +42,8 @@ def parse_args(input_args=None):
     a("--num_denoising_steps", type=int, default=30)
     a("--batch_size", type=int, default=10)
     a("--synthetic", action="store_true", default=False, help="(build addition) synthetic base weights / hash tokenizer")
+    a("--merge_lora", action="store_true", default=False,
+      help="(build addition) fold the LoRA files into the base weights before the models are built (merge.merge_state_dict): no LoRA slab at inference")
     return p.parse_args(input_args) if input_args is not None else p.parse_args()
 
 
@@ -81,6 +85,9 @@ def generate_image(tr, tokens, noises, num_denoising_steps=30, prefix=None):
 
 def main(args, cfgs=None):
     from .lib import WORKING_DTYPE
+    merge = getattr(args, "merge_lora", False)
+    if merge and not (args.load_unet_lora_from or args.load_text_encoder_lora_from):
+        raise ValueError("--merge_lora needs --load_unet_lora_from and / or --load_text_encoder_lora_from: there is nothing to fold")
     if args.mixed_precision != WORKING_DTYPE:
         raise NotImplementedError(f"--mixed_precision {args.mixed_precision}: this process runs the {WORKING_DTYPE} library (fp16 and bf16 are "
                                   "built; select with FD_DTYPE or the flag on the command line; fp32 inference is not built)")
@@ -91,7 +98,7 @@ def main(args, cfgs=None):
     device = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(device)
     cfgs = cfgs or (TINY if os.environ.get("FD_TINY") else SD15)
-    targs = default_args(train_unet=bool(args.load_unet_lora_from), train_text_encoder=bool(args.load_text_encoder_lora_from),
+    targs = default_args(train_unet=bool(args.load_unet_lora_from) and not merge, train_text_encoder=bool(args.load_text_encoder_lora_from) and not merge,
                          rank=args.rank, guidance_scale=args.guidance_scale, pretrained_model_name_or_path=args.pretrained_model_name_or_path)
     state_dicts = None
     if not args.synthetic:
@@ -103,6 +110,16 @@ def main(args, cfgs=None):
         state_dicts["unet_lora"] = torch.load(args.load_unet_lora_from, map_location="cpu")
     if args.load_text_encoder_lora_from:
         state_dicts["te_lora"] = torch.load(args.load_text_encoder_lora_from, map_location="cpu")
+    if merge:
+        # W + up @ down in fp32 before the models round their weights to 16 bit: build_trainer then sees frozen networks only (no bank, no slab).
+        # Under --synthetic the base is the one build_trainer would synthesise (its seed 0: + 1 for the U-Net, + 3 for the text encoder).
+        from . import weights as W
+        from .merge import merge_state_dict
+        for key, lora_key, kind, cfg, shapes, s in (("unet", "unet_lora", "unet", cfgs["unet"], W.unet_param_shapes, 1),
+                                                    ("clip", "te_lora", "text_encoder", cfgs["clip"], W.clip_param_shapes, 3)):
+            if lora_key in state_dicts:
+                base = state_dicts[key] if key in state_dicts else W.synthetic_state_dict(shapes(cfg), seed=0 + s)
+                state_dicts[key] = merge_state_dict(base, state_dicts.pop(lora_key), kind, cfg, device)
     tr, _ = build_trainer(targs, device, cfgs, state_dicts=state_dicts, frozen_copies=False)
     tok_dir = os.path.join(args.pretrained_model_name_or_path, "tokenizer")
     tokenizer = CLIPTokenizerAdapter(tok_dir) if os.path.isdir(tok_dir) else HashTokenizer(cfgs["clip"].vocab_size)

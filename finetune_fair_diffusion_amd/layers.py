@@ -114,14 +114,32 @@ class LoRAPair:
         return self.bank.view(self.dn, self.bank.accum), self.bank.view(self.un, self.bank.accum)
 
 
-def refresh_pairs(pairs, scale=1.0, ema=False):
+def refresh_pairs(pairs, scale=1.0, ema=False, merge=None):
     """Rewrites the 16-bit operand copies of ``pairs`` from their fp32 parameters: ONE call of ``fd_lora_refresh_multi`` (16 pairs per launch)
     instead of ~8 tiny torch launches per pair (128 pairs in the U-Net: 10 ms of host-bound time per optimiser step before).
     ``ema=True`` reads the bank's EMA twin instead (validation of the EMA weights, evaluation.py): only the source pointers differ, no fp32
-    buffer is written; a second call with ``ema=False`` restores the live operands bit for bit."""
+    buffer is written; a second call with ``ema=False`` restores the live operands bit for bit.
+    ``merge=[(base32, out32), ...]``, one entry per pair (fp32 [N, K] device tensors, contiguous; ``out32 is base32`` folds in place): the other
+    derived copy of a pair -- ``out32 = base32 + scale * up @ down`` in fp32 by ONE call of ``fd_lora_merge_multi`` INSTEAD OF the slab refresh
+    (merge.py: a pair that is folded into its base weight has no MFMA slab, so none is allocated or written); ``ema`` and ``scale`` mean the same."""
     import ctypes
     from . import lib as _lib
     pairs = list(pairs)
+    if merge is not None:
+        merge = list(merge)
+        assert len(merge) == len(pairs), "merge= takes one (base32, out32) per pair"
+        if not pairs:
+            return
+        arr = _lib.LoraMergeDesc.array(len(pairs))
+        for d, p, (base, out) in zip(arr, pairs, merge):
+            for t in (base, out):
+                assert t.dtype == F32 and tuple(t.shape) == (p.N, p.K) and t.is_contiguous() and t.device == p.bank.flat.device, (p.un, tuple(t.shape), t.dtype)
+            buf = p.bank.ema if ema else None
+            d.down, d.up = p.bank.view(p.dn, buf).data_ptr(), p.bank.view(p.un, buf).data_ptr()
+            d.base, d.out = base.data_ptr(), out.data_ptr()
+            d.r, d.K, d.N, d.scale = p.r, p.K, p.N, scale
+        ops._call("fd_lora_merge_multi", ctypes.byref(arr), len(pairs), ops._stream())
+        return
     if not pairs:
         return
     arr = _lib.LoraRefreshDesc.array(len(pairs))

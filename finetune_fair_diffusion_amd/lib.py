@@ -77,6 +77,12 @@ class LoraRefreshDesc(_Desc):
                 ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("scale", ctypes.c_float)]
 
 
+class LoraMergeDesc(_Desc):
+    """Mirror of ``fd_lora_merge_desc`` (include/fairdiff_hip.h)."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("down", ctypes.c_void_p), ("up", ctypes.c_void_p), ("base", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("r", ctypes.c_int32), ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
 class CrossBlockDesc(_Desc):
     """Mirror of ``fd_cross_block_desc`` (include/fairdiff_hip.h)."""
     _fields_ = [("struct_size", ctypes.c_int32), ("x", ctypes.c_void_p), ("ln2_gamma", ctypes.c_void_p), ("ln2_beta", ctypes.c_void_p), ("ln2_eps", ctypes.c_float),

@@ -280,6 +280,24 @@ typedef struct fd_lora_refresh_desc {
 } fd_lora_refresh_desc;
 int fd_lora_refresh_multi(const fd_lora_refresh_desc* descs, int n, void* stream);
 
+/* Folding trained LoRA pairs into their base weights (a merged model: what every consumer of a plain Stable-Diffusion directory loads, and the
+ * frozen model's kernels alone at inference), all fp32:   out[n, k] = base[n, k] + scale * sum_{j < r} up[n, j] * down[j, k].
+ * down [r, K], up [N, r], base and out [N, K], rows contiguous; 1 <= r <= 64, no rank padding (the fp32 parameters are read, not the 16-bit copies).
+ * Every pointer needs 4-byte alignment only (down and up are views into a flat parameter bank).  out == base (in place) is allowed; any other
+ * overlap of an out with a base, out, down or up of the call is refused.  Plain VALU, one fma chain per element in ascending j, then one fma with
+ * scale and base: no atomics and no MFMA, so two calls on the same inputs give the same bits.  N == 0 or K == 0 is an empty pair.
+ * Any number of pairs per call (HOST array of descriptors, 16 pairs per launch).  Refused on the host with FD_ERR_ARG before ANYTHING is launched:
+ * a struct_size that is not sizeof(fd_lora_merge_desc), a NULL or misaligned pointer, r outside 1..64, a negative extent, an overlap.
+ * Additive: FD_ABI_VERSION is unchanged. */
+typedef struct fd_lora_merge_desc {
+    int32_t struct_size;                           /* sizeof(fd_lora_merge_desc), checked for every element (see fd_gemm_desc) */
+    const float* down; const float* up;            /* fp32 [r, K], [N, r] */
+    const float* base; float* out;                 /* fp32 [N, K] */
+    int32_t r, K, N;
+    float scale;
+} fd_lora_merge_desc;
+int fd_lora_merge_multi(const fd_lora_merge_desc* descs, int n, void* stream);
+
 /* ---- scheduler / CFG (DPMSolverMultistepScheduler.step + CFG combine, 1-main-debias.py:1051-1056,1123-1131)
  * eps:[2N,4,HW] fp32 NCHW (uncond first); x0_prev/x0_out fp32; lat fp32 updated in place.
  * x0 = (lat - sigma*e)/alpha ; lat' = c_x*lat - c_d0*x0 - c_d1*(x0 - x0_prev)                        */
