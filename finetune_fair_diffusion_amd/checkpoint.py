@@ -10,7 +10,8 @@ Here a checkpoint directory *is* the exported format plus one extra file:
 
     checkpoint-{step}/unet_lora.pth, unet_lora_EMA.pth, text_encoder_lora.pth, text_encoder_lora_EMA.pth
     checkpoint-{step}/prefix_embedding.pth, prefix_embedding_EMA.pth      (exp-2 instead of the LoRA files)
-    checkpoint-{step}/trainer_state.pth   Adam moments (flat fp32 per bank), optimiser / EMA / lr step counters, world size (rank 0 writes it)
+    checkpoint-{step}/trainer_state.pth   Adam moments (flat fp32 per bank), optimiser / EMA / lr step counters, world size (rank 0 writes it);
+                                          ``--experiment custom``: also the resolved target specification, which a resume must match
     checkpoint-{step}/rng_rank{r}.pth     python / numpy / torch / OT-target RNG streams of rank r (every rank writes its own)
 
 so the reference's export step becomes a file copy (``export_checkpoint``), and files exported by the reference load
@@ -113,6 +114,9 @@ def save_state(trainer, save_path, global_step, extra=None):
                   exp_avg={k: b.exp_avg.detach().cpu() for k, b in banks.items()},
                   exp_avg_sq={k: b.exp_avg_sq.detach().cpu() for k, b in banks.items()},
                   world_size=world, extra=extra or {})
+        spec = getattr(trainer, "spec", None)
+        if spec is not None and spec.custom:      # a custom run's resolved target specification; the named experiments' files are unchanged
+            st["spec"] = spec.state()
         torch.save(st, os.path.join(save_path, "trainer_state.pth"))
     else:
         os.makedirs(save_path, exist_ok=True)
@@ -126,8 +130,13 @@ def load_state(trainer, path, seed=None):
     the rank keeps / re-derives its device-specific streams (``seed + rank``, OT 1234 + rank) instead of cloning rank 0's."""
     rank, world = getattr(trainer, "rank", 0), getattr(trainer, "world", 1)
     banks = trainer_banks(trainer)
-    load_lora_files(banks, path)
     st = torch.load(os.path.join(path, "trainer_state.pth"), map_location="cpu", weights_only=False)
+    spec = getattr(trainer, "spec", None)
+    mine = spec.state() if (spec is not None and spec.custom) else None
+    if st.get("spec") != mine:          # refused before anything is copied into the banks
+        raise ValueError(f"checkpoint was trained towards {st.get('spec') or 'a named experiment'}, this run trains towards {mine or 'a named experiment'}: "
+                         "resume with the same --attributes / --target_distribution / --target_solver")
+    load_lora_files(banks, path)
     if st["bank_order"] != list(banks.keys()):
         raise ValueError(f"checkpoint trains {st['bank_order']}, this run trains {list(banks.keys())}")
     for k, b in banks.items():

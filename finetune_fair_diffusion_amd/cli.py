@@ -26,6 +26,26 @@ cannot be set from YAML and booleans follow Python's ``bool(value)`` -- plus the
                          averaged gradient the optimiser saw (null when it is not finite).  One device-side reduction per bank and step, read back
                          asynchronously; off (default): nothing is launched and the line is unchanged
 
+``--experiment custom`` (build addition; no script of the reference: its targets are written into each script's code) keeps exp-1's flags and trains
+towards a target distribution given on the command line or in the YAML; ``fairness.experiment_spec`` resolves and checks them once, and every
+malformed value is refused here with a ValueError that names the flag, before anything is loaded:
+
+  --num_classifier_logits  required: the logit count of the classifier head behind ``--classifier_weight_path``
+  --attributes           "gender:0:2,race:2:4" -- name : first logit column : classes; 1..3 attributes of 2..4 classes each, unique names matching
+                         ``[a-z][a-z0-9_]*``, column ranges disjoint and inside the head
+  --target_distribution  "gender=0.5,0.5;race=0.4,0.2,0.2,0.2" -- per named attribute its k non-negative class probabilities, summing to 1 within
+                         1e-6; an attribute that is not named gets the uniform target
+  --target_solver        rank (one two-class attribute: the binomial rank rule with ``target_ratio = p[0]`` on the device tail, exp-1's),
+                         mc (Monte-Carlo transport plans whose class draws follow the target, exp-3/4/5's) or enumerate (one attribute: the exact
+                         expectation over the class compositions weighted by their multinomial probability, exp-6's); not given: rank for one
+                         two-class attribute, mc otherwise
+  --factor1 / --factor2  one float for every attribute, or a comma list with one float per attribute
+  --face_confidence_level  one float (the named experiments' ``face_*_confidence_level``)
+  --asymmetric_last_attribute  exp-4's cost asymmetry for the last attribute's second class (exp-4 :1551-1556); it exists so that exp-4 can be restated
+
+``--validation`` and ``--train_monitor`` report, per attribute, ``<name>{k}_freq``, ``<name>_pred_below_0.8`` and ``<name>_gap_to_target`` (half the
+L1 distance between the class frequencies and the target) and, with two or more attributes, ``joint_gap_to_target`` over the cells.
+
 The multi-attribute experiments change a few flags and defaults (exp-3-debias-gender-race/1-main-debias.py:343-660,
 exp-4-debias-gender-race-age/...:343-672, exp-5-...:343-690; exp-2-debias-gender-token/...:453-780 drops the two LoRA switches and adds
 ``--train_num_tokens``): ``factor{1,2}`` split per attribute,
@@ -65,7 +85,12 @@ EXPERIMENT_CLI = {
                    val_images_per_prompt_GPU=16, classifier_weight_path=_FF + "GenderRace4_09041216/epoch=9-step=3380_MobileNetLarge.pt",
                    face_feats_path=_MULTI["face_feats_path"]),
               ["face_gender_confidence_level"], dict(face_race_confidence_level=0.9), {}),
+    # custom (build addition): exp-1's flags, one confidence level for whatever the attributes are, the target specification as strings.
+    # factor1 / factor2 hold one float or a comma list, so they are strings here; num_classifier_logits has no default to fall back on (0 = not given)
+    "custom": (dict(factor1="0.2", factor2="0.2"), ["face_gender_confidence_level"], dict(face_confidence_level=0.9),
+               dict(attributes="", target_distribution="", target_solver="")),
 }
+CUSTOM_STR_FLAGS = ("factor1", "factor2")
 
 
 def build_parser(experiment="exp-1"):
@@ -78,11 +103,16 @@ def build_parser(experiment="exp-1"):
             return
         if name in changed:
             kw["default"] = changed[name]
+        if experiment == "custom" and name in CUSTOM_STR_FLAGS:
+            kw["type"] = str
         p.add_argument(flag, **kw)
     for k, v in add_f.items():
         p.add_argument("--" + k, type=float, default=v)
     for k, v in add_s.items():
         p.add_argument("--" + k, type=str, default=v)
+    if experiment == "custom":
+        p.add_argument("--num_classifier_logits", type=int, default=0)
+        p.add_argument("--asymmetric_last_attribute", action="store_true", default=False)
     if experiment == "exp-2":
         p.add_argument("--train_num_tokens", type=int, default=5)       # number of tokens to finetune as prompt prefix (:479-484)
     # 1. experiment setting
@@ -147,13 +177,15 @@ EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="syn
                       train_monitor="off", index_font=None, index_font_size=100, log_norms=False)
 
 
-def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
+def parse_args(input_args=None, with_extras=False, experiment="exp-1", resolve=True):
+    """``resolve=False`` (``factory.default_args``): the defaults of ``custom`` without checking its specification, which is not given yet."""
     p = build_parser(experiment)
     if with_extras:
         p.add_argument("--num_denoising_steps", type=int, default=0, help="0 = draw from range(19,24) like the reference")
         p.add_argument("--synthetic", action="store_true", default=False)
         p.add_argument("--face_provider", type=str, default="synthetic")
-        p.add_argument("--num_classifier_logits", type=int, default=80)
+        if experiment != "custom":
+            p.add_argument("--num_classifier_logits", type=int, default=80)
         p.add_argument("--lora_up_std", type=float, default=0.0)
         p.add_argument("--validation", type=str, default="off", choices=["off", "metrics", "grids", "grids_attrs"])
         p.add_argument("--train_monitor", type=str, default="off", choices=["off", "metrics", "plots"])
@@ -168,6 +200,9 @@ def parse_args(input_args=None, with_extras=False, experiment="exp-1"):
         for key, value in config_data.items():
             d[key] = type(d[key])(value)
         args = argparse.Namespace(**d)
+    if experiment == "custom" and resolve:      # every malformed value of the target specification is refused here
+        from .fairness import experiment_spec
+        experiment_spec(experiment, args)
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1 and env_local_rank != args.local_rank:
         args.local_rank = env_local_rank

@@ -12,7 +12,9 @@ reads ``generated_imgs_dir/prompt_{i}/img_{j}.jpg`` (what ``generate.py`` writes
     :171-263, which the reference's main carries commented out), painted on the device in one launch and saved with ``quality=25``; with
     ``--index_font PATH|default`` each tile carries its image's index as in the reference (:150-151; one more launch, ``evaluation.IndexLabels``);
   * ``metrics.json`` (build addition) -- per prompt and as a mean, exp-4's validation numbers (``evaluation.gap_metrics("exp-4", ...)``) of the three
-    test classifiers' softmax table, tallied on the device (``ops.eval_tally``): 32 integers per prompt are read back for it.
+    test classifiers' softmax table, tallied on the device (``ops.eval_tally``): 32 integers per prompt are read back for it.  With
+    ``--target_distribution "gender=..;race=..;age=.."`` (training's grammar, ``--experiment custom``) it gains a ``target_gaps`` block:
+    ``{gender,race,age}_gap_to_target``, half the L1 distance of the class frequencies to the given target, from the same integers.
 
 Images are decoded on the host (PIL) by a small prefetch pool, uploaded as uint8 HWC and never converted as a whole: the face chips are cropped
 straight from the bytes (``ops.crop_resize_u8``: ``u/255*2-1`` in fp32 per tap, as the reference crops its fp32 tensor) and the grid is painted from
@@ -127,6 +129,9 @@ def parse_args(input_args=None):
            "images to the same text (text_alignment.pkl, text_alignment.json); needs --prompts_path; not given: no such files")
     a("--prompts_path", type=str, default=argparse.SUPPRESS,
       help="(--clip_text_score) the JSON generate.py read: test_prompts[i] is the text of the folder prompt_{i}")
+    a("--target_distribution", type=str, default=argparse.SUPPRESS,
+      help='(build addition) "gender=0.5,0.5;race=0.4,0.2,0.2,0.2;age=0.75,0.25", training\'s grammar over the three test classifiers (an attribute that is '
+           "not named gets the uniform target): adds a target_gaps block to metrics.json; not given: the file as it is without it")
     return p.parse_args(input_args) if input_args is not None else p.parse_args()
 
 
@@ -200,6 +205,28 @@ def warp_affine_u8_host(u8, src_index, A, S, fill=-1.0):
             return np.where(inside[..., None], v, float(fill))
         v = (1 - ly) * ((1 - lx) * tap(y0, x0) + lx * tap(y0, x0 + 1)) + ly * ((1 - lx) * tap(y0 + 1, x0) + lx * tap(y0 + 1, x0 + 1))
         out[k] = v.transpose(2, 0, 1)
+    return out
+
+
+ATTR_NAMES = ("gender", "race", "age")
+
+
+def parse_targets(text):
+    """``--target_distribution`` over the three test classifiers (k = 2, 4, 2) -> [(name, p)], by ``fairness.parse_target_distribution``."""
+    from .fairness import parse_target_distribution
+    attrs = [(n, c0, k) for n, (c0, k) in zip(ATTR_NAMES, TABLE_ATTRS)]
+    return list(zip(ATTR_NAMES, parse_target_distribution(text, attrs)))
+
+
+def target_gaps(counts, targets):
+    """``<name>_gap_to_target`` of the three test classifiers from the 32 integers of ``ops.eval_tally`` / ``evaluation.tally_host``: half the L1
+    distance between the class frequencies (fp32, ``evaluation._freq``) and the target probabilities ``targets`` = [(name, p)]."""
+    from .evaluation import ATTR_STRIDE, OFF_HIST, _freq, gap_to_target
+    c = [int(v) for v in (counts.tolist() if hasattr(counts, "tolist") else counts)]
+    out = {}
+    for a, (name, p) in enumerate(targets):
+        n = c[ATTR_STRIDE * a]
+        out[f"{name}_gap_to_target"] = gap_to_target([_freq(c[ATTR_STRIDE * a + OFF_HIST + k], n).item() for k in range(len(p))], p)
     return out
 
 
@@ -593,6 +620,8 @@ def main(args, face_provider=None, log=print, cfgs=None):
     text_score = bool(getattr(args, "clip_text_score", False))
     if text_score:          # its refusals are host work: before any device work and before anything is written
         texts, text_ids, text_sd = _text_inputs(args, _default_cfgs(cfgs))
+    targets = parse_targets(args.target_distribution) if getattr(args, "target_distribution", None) is not None else None      # refused before any device work
+    gaps = {}
     if not torch.cuda.is_available():
         raise RuntimeError("finetune_fair_diffusion_amd.evaluate_images needs an MI355X (HIP device); there is no CPU path")
     original_dir = getattr(args, "original_imgs_dir", None)
@@ -723,7 +752,10 @@ def main(args, face_provider=None, log=print, cfgs=None):
             probs = [torch.softmax(l, dim=-1) for l in logits]
             table = torch.cat(probs, dim=1)
             table = torch.where(ind.to(device)[:, None], table, torch.full_like(table, -1.0)).contiguous()
-            metrics[prompt_idx] = gap_metrics("exp-4", ops.eval_tally(table, TABLE_ATTRS).cpu())
+            counts = ops.eval_tally(table, TABLE_ATTRS).cpu()
+            metrics[prompt_idx] = gap_metrics("exp-4", counts)
+            if targets is not None:          # from the integers already read back
+                gaps[prompt_idx] = target_gaps(counts, targets)
             if args.grid != "off":
                 grid = device_grid(imgs_d, boxes.to(device), probs, args.grid, labels=labels).cpu().numpy()
                 Image.fromarray(grid).save(os.path.join(args.save_dir, f"prompt_{prompt_idx}.jpg"), quality=25)
@@ -755,6 +787,10 @@ def main(args, face_provider=None, log=print, cfgs=None):
     keys = list(next(iter(metrics.values())).keys()) if metrics else []
     out = {"per_prompt": {str(i): m for i, m in metrics.items()},
            "mean": {k: float(np.array([m[k] for m in metrics.values()]).mean()) for k in keys}}
+    if targets is not None:
+        gkeys = list(next(iter(gaps.values())).keys()) if gaps else []
+        out["target_gaps"] = {"targets": {n: list(p) for n, p in targets}, "per_prompt": {str(i): g for i, g in gaps.items()},
+                              "mean": {k: float(np.array([g[k] for g in gaps.values()]).mean()) for k in gkeys}}
     with open(os.path.join(args.save_dir, "metrics.json"), "w") as f:
         json.dump(_json_safe(out), f, indent=1)
     if pairs is not None:

@@ -74,6 +74,88 @@ def tally_host(probs, attrs):
     return counts
 
 
+def _first_argmax(p):
+    """Index of the first maximum per row: a tie rule the device's ``argmax`` does not promise."""
+    mx = p.max(dim=-1).values
+    cols = torch.arange(p.shape[1], device=p.device).expand_as(p)
+    return torch.where(p == mx[:, None], cols, torch.full_like(cols, p.shape[1])).min(dim=-1).values
+
+
+def joint_tally_host(probs, attrs):
+    """The plain host statement of the joint histogram of a custom run: probs [N, >= sum k] fp32 on the CPU (-1 rows = no face), attrs
+    [(c0, k)] -> int32 [prod k]: how many rows with a face fall into each cell, the first maximum winning per attribute, cells ordered as
+    ``fairness._cells`` (mixed radix over the attributes in order)."""
+    from .fairness import _cells
+    probs = probs.detach().to("cpu", torch.float32)
+    cells = _cells([k for _, k in attrs])
+    hist = torch.zeros(len(cells), dtype=torch.int32)
+    for row in probs:
+        if any(bool((row[c0:c0 + k] == -1).any()) for c0, k in attrs):
+            continue
+        hist[cells.index(tuple(int(row[c0:c0 + k].argmax()) for c0, k in attrs))] += 1
+    return hist
+
+
+def joint_tally(pd, attrs):
+    """``joint_tally_host`` with torch on the table's device (at most ``world x B`` rows and 64 cells): first argmax per attribute, mixed-radix
+    cell index, one ``torch.bincount``; rows without a face are counted in a spare bin that is cut off.  int32 [prod k]."""
+    n_cells = math.prod(k for _, k in attrs)
+    valid = torch.ones(pd.shape[0], dtype=torch.bool, device=pd.device)
+    cell = torch.zeros(pd.shape[0], dtype=torch.long, device=pd.device)
+    for c0, k in attrs:
+        p = pd[:, c0:c0 + k]
+        valid &= (p != -1).all(dim=-1)
+        cell = cell * k + _first_argmax(p)
+    cell = torch.where(valid, cell, torch.full_like(cell, n_cells))
+    return torch.bincount(cell, minlength=n_cells + 1)[:n_cells].to(torch.int32)
+
+
+def tally_with_joint(tr, pd):
+    """The counts of one probability table on the device, as ONE int32 tensor to read back: the 32 integers of ``ops.eval_tally`` and, for a
+    custom run with two or more attributes, the cells of ``joint_tally`` behind them (``split_counts`` takes them apart)."""
+    from . import ops
+    attrs = table_attrs(tr.attrs)
+    counts = ops.eval_tally(pd, attrs)
+    spec = getattr(tr, "spec", None)
+    if spec is not None and spec.custom and len(attrs) >= 2:
+        counts = torch.cat([counts, joint_tally(pd, attrs)])
+    return counts
+
+
+def split_counts(counts):
+    """(the 32 counts, the joint histogram or None) of ``tally_with_joint``'s tensor."""
+    return counts[:N_COUNTS], (counts[N_COUNTS:] if counts.shape[0] > N_COUNTS else None)
+
+
+def gap_to_target(freqs, p):
+    """Half the L1 distance between class frequencies (Python floats holding fp32 values, ``_freq(..).item()``) and the target probabilities:
+    ``(|f0 - p0| + |f1 - p1| + ...) / 2``, as exp-4 writes its ``age_gap`` (exp-4 :1815-1818)."""
+    return sum(abs(f - t) for f, t in zip(freqs, p)) / 2
+
+
+def target_metrics(spec, counts, joint=None):
+    """The validation numbers of a custom run from the integer counts: per attribute ``<name>{k}_freq``, ``<name>_pred_below_0.8`` and
+    ``<name>_gap_to_target``; with two or more attributes ``joint_gap_to_target`` over the cells of ``joint`` (``joint_tally``), whose target is the
+    product of the attributes' marginal targets."""
+    c = [int(v) for v in (counts.tolist() if hasattr(counts, "tolist") else counts)]
+    out = {}
+    for a, at in enumerate(spec.attributes):
+        n, below = c[ATTR_STRIDE * a], c[ATTR_STRIDE * a + OFF_BELOW]
+        f = [_freq(c[ATTR_STRIDE * a + OFF_HIST + k], n).item() for k in range(at.k)]
+        out.update({f"{at.name}{k}_freq": f[k] for k in range(at.k)})
+        out[f"{at.name}_pred_below_0.8"] = _freq(below, n).item()
+        out[f"{at.name}_gap_to_target"] = gap_to_target(f, at.p)
+    if len(spec.attributes) >= 2:
+        from .fairness import _cells
+        if joint is None:
+            raise ValueError("the joint gap of a custom run needs the joint histogram (joint_tally)")
+        j = [int(v) for v in (joint.tolist() if hasattr(joint, "tolist") else joint)]
+        n = sum(j)
+        target = [math.prod(at.p[ci] for at, ci in zip(spec.attributes, cell)) for cell in _cells(spec.sizes)]
+        out["joint_gap_to_target"] = gap_to_target([_freq(v, n).item() for v in j], target)
+    return out
+
+
 def _freq(c, n):
     """``(mask).float().mean()``: the fp32 sum of c ones divided by n in fp32 (NaN for the empty selection, as torch's mean)."""
     return torch.tensor(float(c), dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)
@@ -88,8 +170,13 @@ def _pairwise_gap(freqs):
     return d[~torch.eye(n, dtype=torch.bool)].reshape(n, n - 1).mean().item()
 
 
-def gap_metrics(experiment, counts):
-    """The reference's validation numbers of ``experiment`` from the integer counts of ``tally_host`` / ``ops.eval_tally``."""
+def gap_metrics(experiment, counts, spec=None, joint=None):
+    """The reference's validation numbers of ``experiment`` from the integer counts of ``tally_host`` / ``ops.eval_tally``; for ``custom`` the
+    distances to the target of ``spec`` (``target_metrics``; ``joint``: the cells of ``joint_tally``)."""
+    if experiment == "custom":
+        if spec is None:
+            raise ValueError("the metrics of a custom run need its ExperimentSpec")
+        return target_metrics(spec, counts, joint)
     c = [int(v) for v in (counts.tolist() if hasattr(counts, "tolist") else counts)]
     A = lambda a: (c[ATTR_STRIDE * a], c[ATTR_STRIDE * a + OFF_HIST:ATTR_STRIDE * a + OFF_HIST + 4], c[ATTR_STRIDE * a + OFF_BELOW])
     if experiment in ("exp-1", "exp-2"):
@@ -245,6 +332,16 @@ def grid_inputs_attrs(pd, attrs):
     return preds.to(torch.int32).contiguous(), probs, grid_attrs_bar_rows(probs), device_order(preds, probs)
 
 
+def strip_palettes(tr):
+    """One palette per strip, index = pred + 1.  The named experiments: gender, race, age, the reference's.  A custom run: by class count -- two
+    classes the gender palette, four the race palette, three its first three class colours."""
+    from .evaluate_images import PALETTES
+    spec = getattr(tr, "spec", None)
+    if spec is None or not spec.custom:
+        return PALETTES[:len(tr.attrs)]
+    return [PALETTE_GENDER if k == 2 else PALETTE_RACE[:k + 1] for k in spec.sizes]
+
+
 def device_grid_attrs(tr, images, boxes, pd, labels=None):
     """The annotated grid with one strip per attribute (uint8 on the device), one launch of ``ops.eval_grid_attrs_img``: exp-3/5 gender and race
     (``plot_in_grid_gender_race``), exp-4 gender, race and age (``plot_in_grid_gender_race_age``).  The one-attribute experiments have their own
@@ -253,11 +350,11 @@ def device_grid_attrs(tr, images, boxes, pd, labels=None):
     if len(tr.attrs) == 1:
         return device_grid(tr, images, boxes, pd, labels=labels)
     from . import ops
-    from .evaluate_images import PALETTES
     n = len(tr.attrs)
     preds, _, bar_rows, order = grid_inputs_attrs(pd, table_attrs(tr.attrs))
-    P = max(len(p) for p in PALETTES[:n])
-    pal = torch.tensor([p + [(255, 255, 255)] * (P - len(p)) for p in PALETTES[:n]], dtype=torch.uint8, device=images.device)
+    palettes = strip_palettes(tr)
+    P = max(len(p) for p in palettes)
+    pal = torch.tensor([p + [(255, 255, 255)] * (P - len(p)) for p in palettes], dtype=torch.uint8, device=images.device)
     grid = ops.eval_grid_attrs_img(images.contiguous(), order, boxes.to(images.device, torch.int32).contiguous(), preds, bar_rows, pal)
     return draw_labels(grid, order, labels, images.shape[2], images.shape[3], n)
 
@@ -464,10 +561,10 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
     ``eval_{name}_{step}_{prompt}_{ori|generated}.jpg`` showing the first attribute; with ``"grids_attrs"`` the grids of exp-3/4/5 carry one strip
     per attribute (``device_grid_attrs``; the other experiments' files are the same in both modes); with ``"metrics"`` the frozen pass, which only
     feeds its grid, is not generated.  A trainer that carries ``index_labels`` (``--index_font``) gets the index text on every grid."""
-    from . import ops
     tr = trainer
     logs = []
     tr.last_eval_counts = []          # the int32 counts behind ``logs``, per prompt (what the tests compare with the host tally)
+    tr.last_eval_joint = []           # custom runs with two or more attributes: the joint histogram read back with them, else None
     te_o, unet_o = _frozen_pair(tr)
     for (prompt, toks), noises_i in zip(prompts_tokens, noises):
         nd = noises_i.to(tr.device, torch.float32)
@@ -484,9 +581,10 @@ def evaluate_process(trainer, which, name, prompts_tokens, noises, step, mode="m
             h = tr.classify_begin(images)
             pd = _gather_dev(tr, probability_table(tr, h))
             if tag == "generated":
-                counts = ops.eval_tally(pd, table_attrs(tr.attrs)).cpu()          # the evaluation's read-back: 32 integers
+                counts, joint = split_counts(tally_with_joint(tr, pd).cpu())          # the evaluation's read-back: 32 integers (custom: and the cells)
                 tr.last_eval_counts.append(counts)
-                logs.append(gap_metrics(tr.experiment, counts))
+                tr.last_eval_joint.append(joint)
+                logs.append(gap_metrics(tr.experiment, counts, getattr(tr, "spec", None), joint))
             if grids:
                 images_all, boxes_all = _gather_dev(tr, images), _gather_dev(tr, h["boxes"].to(tr.device, torch.int32))
                 if tr.rank == 0:

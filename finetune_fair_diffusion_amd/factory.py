@@ -43,7 +43,7 @@ def synthetic_tokens(L=13, vocab=49408, seed=1):
 
 def default_args(experiment="exp-1", **kw):
     from .cli import parse_args
-    a = vars(parse_args([], experiment=experiment))
+    a = vars(parse_args([], experiment=experiment, resolve=False))
     a.update(kw)
     return types.SimpleNamespace(**a)
 
@@ -59,8 +59,8 @@ def build_trainer(args, device, cfgs=SD15, seed=0, rank=0, world_size=1, experim
     ``lora_up_std``: fresh LoRA ``up`` matrices are ZERO, exactly like diffusers' ``LoRALinearLayer`` / ``_modify_text_encoder``
     (:798-818, :829-883), so the finetuned model equals the frozen original at step 0 and R1 == R2.  Only synthetic bench / smoke /
     test runs pass a non-zero std (the "one warm-up optimiser step" of SURVEY 8d) so that dL/d(down) is non-zero on the first step."""
-    from .fairness import EXPERIMENT_ATTRS
-    num_classes = EXPERIMENT_ATTRS[experiment][0]
+    from .fairness import experiment_spec
+    num_classes = experiment_spec(experiment, args).num_logits
     train_prefix = experiment == "exp-2"          # prefix-token tuning: no LoRA anywhere, both networks frozen (exp-2 :946)
     if not hasattr(args, "train_unet"):           # exp-2's CLI has neither switch
         args.train_unet = False

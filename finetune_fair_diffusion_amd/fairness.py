@@ -5,7 +5,9 @@ face-box expansion (:238-265), the face-provider seam that replaces the insightf
 per-image loss weights (:1619-1633) and the distributional-alignment loss gradient (:1912-1933).
 Pinned against the reference's own outputs by tests/golden/reference_pure_functions.json.
 """
+import dataclasses
 import math
+import re
 
 import numpy as np
 import scipy.stats
@@ -420,29 +422,48 @@ _COMPOSITION_TABLES = {}
 TABLE_MASS = 0.95
 
 
-def composition_table(N, K=4):
-    """The compositions of N faces into K = 4 race classes that exp-6 transports onto (exp-6-debias-race/1-main-debias.py:1439-1454), cached
-    per N: ``(counts [S, 4] int32, weights [S] float64)`` in kept order.
+def _compositions(N, K):
+    """Every composition of N into K parts with the first part outermost, and its multinomial coefficient as an exact Python int."""
+    def rec(prefix, left, coef):
+        if len(prefix) == K - 1:
+            yield prefix + (left,), coef
+            return
+        for n in range(left + 1):
+            yield from rec(prefix + (n,), left - n, coef * math.comb(left, n))
+    return rec((), N, 1)
 
-    Every composition (n1, .., n4) -- enumerated with n1 outermost -- carries its multinomial coefficient (exact Python ints; numpy makes an
+
+def composition_table(N, K=4, p=None):
+    """The compositions of N faces into K classes that the exact-enumeration targets transport onto (K = 4, uniform: exp-6's race classes,
+    exp-6-debias-race/1-main-debias.py:1439-1454), cached per (N, K, p): ``(counts [S, K] int32, weights [S] float64)`` in kept order.
+
+    Every composition (n1, .., nK) -- enumerated with n1 outermost -- carries its multinomial coefficient (exact Python ints; numpy makes an
     int64 array up to N = 35 and an object array from 36 on, where the coefficients overflow int64), normalised by ``np.linalg.norm(ord=1)``.
     The weights are sorted descending and kept until their sequential running sum exceeds 0.95 (strict).  The sort is
     ``np.flip(np.argsort(w, kind="stable"))``: the reference's expression with a stable sort, so that the kept set does not depend on the CPU
     (numpy's default float sort is SIMD-dispatched and orders the equal-weight compositions at the cutoff differently on different machines;
-    only the membership of that cutoff tie group can differ from a given reference run).  N = 0: an empty table."""
-    assert K == 4
-    tab = _COMPOSITION_TABLES.get(N)
+    only the membership of that cutoff tie group can differ from a given reference run).  N = 0: an empty table.
+
+    ``p``: target class probabilities (K in 2..4; ``--experiment custom``): the weight of a composition is the multinomial probability, its
+    exact integer coefficient as a float times ``prod(p_k ** n_k)`` in fp64, normalised the same way.  None, or the uniform p at K = 4: the
+    table of exp-6, the same cached object."""
+    assert 2 <= K <= 4, K
+    if p is not None:
+        p = tuple(float(v) for v in p)
+        assert len(p) == K, (p, K)
+        if K == 4 and p == (0.25, 0.25, 0.25, 0.25):
+            p = None
+    key = N if (K == 4 and p is None) else (N, K, p)
+    tab = _COMPOSITION_TABLES.get(key)
     if tab is not None:
         return tab
     if N == 0:
         tab = (np.zeros((0, K), dtype=np.int32), np.zeros(0, dtype=np.float64))
     else:
         combs, coefs = [], []
-        for n1 in range(N + 1):
-            for n2 in range(N - n1 + 1):
-                for n3 in range(N - n1 - n2 + 1):
-                    combs.append((n1, n2, n3, N - n1 - n2 - n3))
-                    coefs.append(math.comb(N, n1) * math.comb(N - n1, n2) * math.comb(N - n1 - n2, n3))
+        for comb, coef in _compositions(N, K):
+            combs.append(comb)
+            coefs.append(coef if p is None else float(coef) * math.prod(pk ** nk for pk, nk in zip(p, comb)))
         w = np.array(coefs)
         w = w / np.linalg.norm(w, ord=1)
         order = np.flip(np.argsort(w, kind="stable"))
@@ -453,12 +474,12 @@ def composition_table(N, K=4):
                 break
         keep = order[:last + 1]
         tab = (np.array(combs, dtype=np.int32)[keep], np.asarray(w[keep], dtype=np.float64))
-    _COMPOSITION_TABLES[N] = tab
+    _COMPOSITION_TABLES[key] = tab
     return tab
 
 
 @torch.no_grad()
-def expected_transport_targets(probs, device=None, table=None):
+def expected_transport_targets(probs, device=None, table=None, p=None):
     """exp-6's dynamic targets (``generate_dynamic_targets_race``, exp-6-debias-race/1-main-debias.py:1414-1483) for the gathered race
     probabilities ``probs`` [n, 4] (-1 rows = no face): for every kept composition of the N faces (``composition_table``) the exact transport
     ``ot.emd(ones(N), counts_s, M)`` onto the one-hot corners, the plans summed with the composition weights (sequentially, in table order,
@@ -467,7 +488,7 @@ def expected_transport_targets(probs, device=None, table=None):
 
     ``device``: solve and reduce on that GPU (``fd_ot_expected_targets``: one wave per composition, then one thread per face -- bit-equal to the
     host statement wherever the optimal plans are unique); None: scipy's assignment per composition.  ``table``: (counts, weights) to use instead
-    of the cached one (tests inject a recorded reference table)."""
+    of the cached one (tests inject a recorded reference table).  ``p``: the target class probabilities of ``composition_table`` (None: uniform)."""
     probs = probs.detach().cpu()
     n = probs.shape[0]
     idx = (probs != -1).all(dim=-1)
@@ -477,7 +498,7 @@ def expected_transport_targets(probs, device=None, table=None):
     if N == 0:
         return t_all, u_all
     M = _corner_cost([probs[idx].float().numpy()], [probs.shape[1]])
-    counts, weights = composition_table(N, probs.shape[1]) if table is None else table
+    counts, weights = composition_table(N, probs.shape[1], p) if table is None else table
     counts = np.asarray(counts, dtype=np.int32)
     weights = np.asarray(weights, dtype=np.float64)
     if device is not None:
@@ -517,3 +538,198 @@ EXPERIMENT_ATTRS = {
     "exp-5": (6, [("gender", 0, 2), ("race", 2, 4)], [[0.5, 1.0], [0.25, 0.5, 0.75, 1.0]], False),
     "exp-6": (6, [("race", 2, 4)], None, False),      # race alone on the GenderRace4 head: exact-enumeration targets (expected_transport_targets)
 }
+
+
+# ------------------------------------------------------------------------------------------ the resolved target specification
+# target class probabilities of the named experiments' attributes: balanced gender and race, 75 % young / 25 % old (exp-4 `:1504`)
+_NAMED_TARGETS = {"gender": (0.5, 0.5), "race": (0.25, 0.25, 0.25, 0.25), "age": (0.75, 0.25)}
+_NAMED_SOLVERS = {"exp-1": "rank", "exp-2": "rank", "exp-3": "mc", "exp-4": "mc", "exp-5": "mc", "exp-6": "enumerate"}
+SOLVERS = ("rank", "mc", "enumerate")
+CUSTOM_MAX_ATTR, CUSTOM_MIN_K, CUSTOM_MAX_K = 3, 2, 4          # FD_EVAL_MAX_ATTR / FD_EVAL_MAX_K: the tally and the painters serve every custom run
+
+
+@dataclasses.dataclass(frozen=True)
+class AttributeSpec:
+    """One attribute of the classifier head: its name, first logit column, class count and target class probabilities."""
+    name: str
+    column: int
+    k: int
+    p: tuple
+
+    @property
+    def cdf(self):
+        """Upper CDF edges of the Monte-Carlo class draw: the running fp64 sums of ``p``, the last edge exactly 1."""
+        edges = [float(v) for v in np.cumsum(np.asarray(self.p, dtype=np.float64))]
+        edges[-1] = 1.0
+        return edges
+
+
+@dataclasses.dataclass(frozen=True)
+class ExperimentSpec:
+    """What an experiment trains towards, resolved once (``experiment_spec``): the classifier's logit count, the attributes with their targets,
+    how the dynamic targets are solved -- "rank" (one binary attribute: the binomial rank rule on the device tail), "mc" (Monte-Carlo transport
+    plans) or "enumerate" (one attribute: the exact expectation over class compositions) --, exp-4's cost asymmetry for the last attribute's
+    second class, and the names of the flags that carry the regulariser factors and the face confidence level."""
+    experiment: str
+    num_logits: int
+    attributes: tuple
+    solver: str
+    asymmetric_last: bool
+    factor1_flags: tuple
+    factor2_flags: tuple
+    confidence_flag: str
+
+    @property
+    def attrs(self):
+        """[(name, first logit column, k)], the form the step and the evaluation helpers take."""
+        return [(a.name, a.column, a.k) for a in self.attributes]
+
+    @property
+    def sizes(self):
+        return [a.k for a in self.attributes]
+
+    @property
+    def class_cdfs(self):
+        """Per attribute the CDF edges of the Monte-Carlo draws; None for the solvers that draw nothing."""
+        return [a.cdf for a in self.attributes] if self.solver == "mc" else None
+
+    @property
+    def custom(self):
+        return self.experiment == "custom"
+
+    def regulariser_values(self, args):
+        """(factors1, factors2, face confidence level), one factor per attribute.  A single flag serving several attributes (``custom``) holds
+        one float for all of them or a comma list with one float per attribute."""
+        n = len(self.attributes)
+        out = []
+        for flags in (self.factor1_flags, self.factor2_flags):
+            if len(flags) == n and not self.custom:
+                out.append([getattr(args, k) for k in flags])
+            else:
+                out.append(_float_list("--" + flags[0], getattr(args, flags[0]), n))
+        return out[0], out[1], float(getattr(args, self.confidence_flag))
+
+    def state(self):
+        """Plain data for a checkpoint: equal exactly when two runs train towards the same thing."""
+        return dict(experiment=self.experiment, num_logits=self.num_logits, solver=self.solver, asymmetric_last=self.asymmetric_last,
+                    attributes=[(a.name, a.column, a.k, tuple(a.p)) for a in self.attributes])
+
+
+def _float_list(flag, value, n):
+    """One float for all n attributes, or a comma list with one float per attribute."""
+    parts = [value] if isinstance(value, (int, float)) else [v.strip() for v in str(value).split(",")]
+    try:
+        vals = [float(v) for v in parts]
+    except ValueError:
+        raise ValueError(f"{flag} {value!r}: one float, or a comma list with one float per attribute") from None
+    if len(vals) == 1:
+        return vals * n
+    if len(vals) != n:
+        raise ValueError(f"{flag} {value!r}: {len(vals)} numbers for {n} attributes (one for all, or one per attribute)")
+    return vals
+
+
+def parse_attributes(text, num_logits, flag="--attributes"):
+    """``"gender:0:2,race:2:4"`` -> [(name, first logit column, classes)]: 1..3 attributes of 2..4 classes, unique names matching
+    ``[a-z][a-z0-9_]*``, column ranges disjoint and inside the ``num_logits`` classifier logits."""
+    items = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not 1 <= len(items) <= CUSTOM_MAX_ATTR:
+        raise ValueError(f"{flag} {text!r}: {len(items)} attributes, 1..{CUSTOM_MAX_ATTR} are supported")
+    out, used = [], set()
+    for item in items:
+        parts = item.split(":")
+        if len(parts) != 3 or not re.fullmatch(r"[a-z][a-z0-9_]*", parts[0]) or not parts[1].isdigit() or not parts[2].isdigit():
+            raise ValueError(f"{flag} {item!r}: expected name:first_logit_column:classes with a name matching [a-z][a-z0-9_]*")
+        name, c0, k = parts[0], int(parts[1]), int(parts[2])
+        if name in {n for n, _, _ in out}:
+            raise ValueError(f"{flag} {text!r}: attribute {name!r} is named twice")
+        if not CUSTOM_MIN_K <= k <= CUSTOM_MAX_K:
+            raise ValueError(f"{flag} {item!r}: {k} classes, {CUSTOM_MIN_K}..{CUSTOM_MAX_K} are supported")
+        if c0 + k > num_logits:
+            raise ValueError(f"{flag} {item!r}: columns {c0}..{c0 + k - 1} lie outside the {num_logits} classifier logits (--num_classifier_logits)")
+        if used & set(range(c0, c0 + k)):
+            raise ValueError(f"{flag} {text!r}: the columns of {name!r} overlap another attribute's")
+        used |= set(range(c0, c0 + k))
+        out.append((name, c0, k))
+    return out
+
+
+def parse_target_distribution(text, attrs, flag="--target_distribution"):
+    """``"gender=0.5,0.5;race=0.4,0.2,0.2,0.2"`` -> per attribute of ``attrs`` its k target probabilities (a tuple of floats): every named
+    attribute gets k non-negative numbers that sum to 1 within 1e-6; an attribute that is not named gets the uniform target."""
+    given = {}
+    for item in [t.strip() for t in str(text or "").split(";") if t.strip()]:
+        name, eq, nums = item.partition("=")
+        name = name.strip()
+        if not eq or name not in {n for n, _, _ in attrs}:
+            raise ValueError(f"{flag} {item!r}: expected one of {[n for n, _, _ in attrs]} followed by =p0,p1,...")
+        if name in given:
+            raise ValueError(f"{flag} {text!r}: attribute {name!r} is named twice")
+        try:
+            vals = tuple(float(v) for v in nums.split(","))
+        except ValueError:
+            raise ValueError(f"{flag} {item!r}: the probabilities must be numbers") from None
+        k = {n: kk for n, _, kk in attrs}[name]
+        if len(vals) != k:
+            raise ValueError(f"{flag} {item!r}: {len(vals)} numbers for the {k} classes of {name!r}")
+        if any(not (v >= 0) or math.isinf(v) for v in vals):
+            raise ValueError(f"{flag} {item!r}: probabilities must be non-negative")
+        if abs(math.fsum(vals) - 1.0) > 1e-6:
+            raise ValueError(f"{flag} {item!r}: the probabilities sum to {math.fsum(vals)!r}, not 1")
+        given[name] = vals
+    return [given.get(n, tuple([1.0 / k] * k)) for n, _, k in attrs]
+
+
+def custom_spec(args):
+    """The ``ExperimentSpec`` of ``--experiment custom`` from the parsed flags; every malformed value raises ValueError naming its flag."""
+    num_logits = int(getattr(args, "num_classifier_logits", 0) or 0)
+    if num_logits < 1:
+        raise ValueError("--num_classifier_logits is required with --experiment custom (the classifier head's logit count)")
+    attrs = parse_attributes(getattr(args, "attributes", ""), num_logits)
+    targets = parse_target_distribution(getattr(args, "target_distribution", ""), attrs)
+    binary_single = len(attrs) == 1 and attrs[0][2] == 2
+    solver = getattr(args, "target_solver", None) or ("rank" if binary_single else "mc")
+    if solver not in SOLVERS:
+        raise ValueError(f"--target_solver {solver!r}: one of {', '.join(SOLVERS)}")
+    if solver == "rank" and not binary_single:
+        raise ValueError("--target_solver rank needs exactly one two-class attribute (--attributes)")
+    if solver == "enumerate" and len(attrs) != 1:
+        raise ValueError("--target_solver enumerate needs exactly one attribute (--attributes)")
+    spec = ExperimentSpec("custom", num_logits, tuple(AttributeSpec(n, c0, k, p) for (n, c0, k), p in zip(attrs, targets)), solver,
+                          bool(getattr(args, "asymmetric_last_attribute", False)), ("factor1",), ("factor2",), "face_confidence_level")
+    for flag in ("factor1", "factor2"):
+        if hasattr(args, flag):
+            _float_list("--" + flag, getattr(args, flag), len(attrs))
+    if hasattr(args, "face_confidence_level"):
+        try:
+            float(args.face_confidence_level)
+        except (TypeError, ValueError):
+            raise ValueError(f"--face_confidence_level {args.face_confidence_level!r}: one float") from None
+    return spec
+
+
+def experiment_spec(experiment, args=None):
+    """The ``ExperimentSpec`` of an experiment: a row of ``EXPERIMENT_ATTRS`` / ``EXPERIMENT_REG_FLAGS`` for the six named ones (``args`` is
+    not read), the parsed flags of ``args`` for ``custom``."""
+    if experiment == "custom":
+        if args is None:
+            raise ValueError("--experiment custom is defined by its flags (--attributes, --target_distribution, ...)")
+        return custom_spec(args)
+    num_logits, attrs, _, asym = EXPERIMENT_ATTRS[experiment]
+    f1, f2, conf = EXPERIMENT_REG_FLAGS[experiment]
+    return ExperimentSpec(experiment, num_logits, tuple(AttributeSpec(n, c0, k, _NAMED_TARGETS[n]) for n, c0, k in attrs),
+                          _NAMED_SOLVERS[experiment], asym, tuple(f1), tuple(f2), conf)
+
+
+@torch.no_grad()
+def spec_dynamic_targets(spec, probs_list, generator=None, num_samples_per_device=100, allreduce=None, device=None):
+    """The host statement of an experiment's dynamic targets: per attribute (targets [n] long, uncertainty [n]) from the gathered probabilities
+    ``probs_list`` (per attribute a CPU tensor [n, k], -1 rows = no face), by the spec's solver -- ``generate_dynamic_targets`` with
+    ``target_ratio = p[0]``, ``generate_dynamic_targets_multi`` on the spec's CDF edges, or ``expected_transport_targets`` on the composition
+    table of ``p``."""
+    if spec.solver == "rank":
+        return [generate_dynamic_targets(probs_list[0], target_ratio=spec.attributes[0].p[0], w_uncertainty=True)]
+    if spec.solver == "enumerate":
+        return [expected_transport_targets(probs_list[0], device=device, p=spec.attributes[0].p)]
+    return generate_dynamic_targets_multi(probs_list, spec.class_cdfs, num_samples_per_device, generator, allreduce,
+                                          age_asymmetric=spec.asymmetric_last, device=device)

@@ -32,7 +32,8 @@ def dynamic_targets(probs, tables, threshold=None, target_ratio=0.5):
     rank = torch.empty_like(order)
     rank[order] = torch.arange(n, device=probs.device)
     nv = valid.sum()
-    t = (rank.to(torch.float32) >= nv.to(torch.float32) * target_ratio).long()
+    # the host compares the integer rank with the Python double ``n * target_ratio`` in fp32: the product in fp64, one rounding to fp32
+    t = (rank.to(torch.float32) >= (nv.to(torch.float64) * target_ratio).to(torch.float32)).long()
     r = rank.clamp(max=tables[0].shape[1] - 1)
     unc = torch.where(t == 1, tables[1][nv, r], tables[0][nv, r])
     targets = torch.where(valid, t, torch.full_like(t, -1))

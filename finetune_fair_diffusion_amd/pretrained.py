@@ -152,12 +152,12 @@ def load_regularisers(args, cfgs):
 
 def load_pretrained(args, cfgs):
     """-> dict for factory.build_trainer(state_dicts=...)."""
-    from .fairness import EXPERIMENT_ATTRS
+    from .fairness import experiment_spec
     m = args.pretrained_model_name_or_path
     if not os.path.isdir(m):
         raise FileNotFoundError(f"{m}: not a local diffusers directory (no network here; pass --synthetic for synthetic weights)")
     experiment = getattr(args, "experiment", "exp-1")
     out = dict(unet=load_unet(m, cfgs["unet"]), vae=load_vae(m, cfgs["vae"]), clip=load_text_encoder(m, cfgs["clip"]))
-    out["clf"] = load_classifier(args.classifier_weight_path, EXPERIMENT_ATTRS[experiment][0])
+    out["clf"] = load_classifier(args.classifier_weight_path, experiment_spec(experiment, args).num_logits)
     out.update(load_regularisers(args, cfgs))
     return out

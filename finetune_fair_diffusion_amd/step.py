@@ -38,7 +38,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import ops
-from .fairness import (EXPERIMENT_ATTRS, EXPERIMENT_REG_FLAGS, SyntheticFaceProvider, composition_table, expected_transport_targets,
+from .fairness import (SyntheticFaceProvider, composition_table, expected_transport_targets, experiment_spec,
                        face_grad_factors, face_grad_factors_multi, fair_loss_and_grad, gen_dynamic_weights, gen_dynamic_weights_multi,
                        generate_dynamic_targets, mc_transport_plan, microbatch_weights, targets_from_plan)
 from . import fairness_dev as FD
@@ -166,23 +166,26 @@ class FairnessTrainer:
         if self.use_img_loss and not self.use_face_loss and getattr(args, "weight_loss_face", 0) != 0:
             raise ValueError("weight_loss_face != 0 but no face-feature network / database is attached "
                              "(build_trainer(..., regularisers=True) attaches them; or pass --weight_loss_face 0)")
-        f1, f2, conf = EXPERIMENT_REG_FLAGS[experiment]
+        # what this run trains towards, resolved once (fairness.ExperimentSpec): everything below reads the record, not the experiment's name
+        self.spec = spec = experiment_spec(experiment, args)
         if self.use_img_loss or self.use_face_loss:
-            self.factors1, self.factors2 = [getattr(args, k) for k in f1], [getattr(args, k) for k in f2]
-            self.face_conf = getattr(args, conf)
+            self.factors1, self.factors2, self.face_conf = spec.regulariser_values(args)
         self.te, self.unet, self.vae, self.clf, self.sch = text_encoder, unet, vae, classifier, scheduler
         self.eval_te = eval_text_encoder if eval_text_encoder is not None else text_encoder
         self.eval_unet = eval_unet if eval_unet is not None else unet
         self.faces = face_provider or SyntheticFaceProvider()
         # which classifier columns carry which attribute (exp-1: CelebA attr 20 of 40x2 logits `:1370`; exp-3/5: 2+4; exp-4: 2+4+2)
         self.experiment = experiment
-        _, self.attrs, self.class_cdfs, self.age_asym = EXPERIMENT_ATTRS[experiment]
+        self.attrs, self.class_cdfs, self.age_asym = spec.attrs, spec.class_cdfs, spec.asymmetric_last
         # exp-1 (one binary attribute): probabilities, dynamic targets, loss, dynamic weights and hook factors stay ON THE DEVICE (fairness_dev.py);
         # what the caller is told about the step (probabilities, targets, per-image losses) comes back in ONE read-back together with the
         # finite flag.  The multi-attribute experiments and exp-6 keep the host path (their OT solve has its own worker thread / device solver).
-        self.device_tail = experiment in ("exp-1", "exp-2") and len(self.attrs) == 1 and self.attrs[0][2] == 2 and not _HOST_TAIL
+        self.device_tail = spec.solver == "rank" and not _HOST_TAIL
+        # the rank rule's share of class 0 (exp-1 / exp-2: 0.5) and, for the enumeration, the target class probabilities (exp-6: uniform = None)
+        self.target_ratio = spec.attributes[0].p[0] if spec.solver == "rank" else 0.5
+        self.target_p = spec.attributes[0].p if (spec.solver == "enumerate" and spec.custom) else None
         # exp-6: one 4-class attribute whose targets are the expected transport plan over the exact enumeration of class compositions
-        self.enumerated_targets = experiment == "exp-6"
+        self.enumerated_targets = spec.solver == "enumerate"
         self._binom = {}
         self._pending_readback = None
         self.target_rng = torch.Generator().manual_seed(1234 + rank)
@@ -278,7 +281,7 @@ class FairnessTrainer:
         self.log_norms = False
         self.last_norms = self._norms_host = None
         if self.enumerated_targets:      # the table of the usual global face count (every image has a face); other counts are built on the worker
-            composition_table(world_size * getattr(args, "train_images_per_prompt_GPU", 0))
+            composition_table(world_size * getattr(args, "train_images_per_prompt_GPU", 0), self.attrs[0][2], self.target_p)
 
     # ------------------------------------------------------------------ per-phase timing (R1 / R2 / R3-fwd / R3-bwd / sync)
     def _mark(self, name):
@@ -519,7 +522,7 @@ class FairnessTrainer:
 
     def _binom_tables(self, n):
         if n not in self._binom:
-            self._binom[n] = tuple(t.to(self.device) for t in FD.binomial_tables(n))
+            self._binom[n] = tuple(t.to(self.device) for t in FD.binomial_tables(n, getattr(self, "target_ratio", 0.5)))
         return self._binom[n]
 
     def classify(self, images, record=False):
@@ -579,7 +582,8 @@ class FairnessTrainer:
                 gl = [torch.empty_like(pd) for _ in range(self.world)]
                 dist.all_gather(gl, pd.contiguous())
                 pd = torch.cat(gl)
-            t_all, u_all = FD.dynamic_targets(pd, self._binom_tables(pd.shape[0]), threshold=self.args.uncertainty_threshold)
+            t_all, u_all = FD.dynamic_targets(pd, self._binom_tables(pd.shape[0]), threshold=self.args.uncertainty_threshold,
+                                              target_ratio=getattr(self, "target_ratio", 0.5))
             self._tgt = dict(B=B, dev=[(t_all[B * self.rank:B * (self.rank + 1)], u_all[B * self.rank:B * (self.rank + 1)])])
             return
         if not self.collectives:
@@ -591,12 +595,14 @@ class FairnessTrainer:
                 gathered.append(allp[:, c:c + k].contiguous())
                 c += k
         enumerated = getattr(self, "enumerated_targets", False)
-        self._tgt = dict(B=B, single=len(per) == 1 and not enumerated)
+        spec = getattr(self, "spec", None)
+        self._tgt = dict(B=B, single=(len(per) == 1 and not enumerated) if spec is None else spec.solver == "rank")
         if self._tgt["single"]:
-            self._tgt["res"] = [generate_dynamic_targets(gathered[0], w_uncertainty=True)]
+            self._tgt["res"] = [generate_dynamic_targets(gathered[0], target_ratio=getattr(self, "target_ratio", 0.5), w_uncertainty=True)]
             return
 
         st = self._tgt
+        target_p = getattr(self, "target_p", None)
 
         def work():
             t0 = time.perf_counter()
@@ -604,10 +610,10 @@ class FairnessTrainer:
                 if enumerated:
                     if self.ot_on_device:       # inputs up, solves, reduction and the read-back all on the side stream of this thread
                         with torch.cuda.stream(self._ot_stream):
-                            t, u = expected_transport_targets(gathered[0], device=self.device)
+                            t, u = expected_transport_targets(gathered[0], device=self.device, p=target_p)
                         self._ot_stream.synchronize()
                     else:
-                        t, u = expected_transport_targets(gathered[0])
+                        t, u = expected_transport_targets(gathered[0], p=target_p)
                     st["res"] = [(t, u.float())]
                 elif self.ot_on_device:       # fd_ot_assign_sum on a side stream of this thread; the summed plan stays in HBM for the all-reduce
                     with torch.cuda.stream(self._ot_stream):
@@ -717,7 +723,7 @@ class FairnessTrainer:
         pd = EV._gather_dev(self, EV.probability_table(self, h))
         mon["tables"][tag] = pd
         if tally:
-            mon["counts"] = self._to_pinned(ops.eval_tally(pd, EV.table_attrs(self.attrs)))
+            mon["counts"] = self._to_pinned(EV.tally_with_joint(self, pd))
         if plot:
             images_all = EV._gather_dev(self, images)
             bx = h["boxes"].to(torch.int32)

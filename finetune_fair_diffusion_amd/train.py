@@ -1,7 +1,9 @@
 """Training driver: the loop of exp-1-debias-gender/1-main-debias.py ``main`` (:647-2070) around FairnessTrainer.
 
-    python -m finetune_fair_diffusion_amd.train [--experiment exp-1|exp-2|exp-3|exp-4|exp-5|exp-6] --config <yaml> [--synthetic]
+    python -m finetune_fair_diffusion_amd.train [--experiment exp-1|exp-2|exp-3|exp-4|exp-5|exp-6|custom] --config <yaml> [--synthetic]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m finetune_fair_diffusion_amd.train ...
+
+``--experiment custom`` trains towards a target distribution given by ``--attributes`` / ``--target_distribution`` / ``--target_solver`` (cli.py).
 
 Same flags, YAML overlay, seeding (``set_seed(seed, device_specific=True)`` :693, prompt order from
 ``random.seed(seed+1)`` :914-921, S drawn on rank 0 from range(19,24) and broadcast :1779-1781, per-rank CPU noise
@@ -163,7 +165,7 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
     if experiment is None:       # build addition: one driver for the reference's per-experiment scripts
         import argparse
         pre = argparse.ArgumentParser(add_help=False)
-        pre.add_argument("--experiment", default="exp-1", choices=["exp-1", "exp-2", "exp-3", "exp-4", "exp-5", "exp-6"])
+        pre.add_argument("--experiment", default="exp-1", choices=["exp-1", "exp-2", "exp-3", "exp-4", "exp-5", "exp-6", "custom"])
         ns, argv = pre.parse_known_args(argv)
         experiment = ns.experiment
     args = parse_args(argv, with_extras=True, experiment=experiment)
@@ -309,9 +311,10 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
                        p_class1_mean=float(out["probs"][:, 1][out["probs"][:, 1] != -1].mean()) if bool((out["probs"] != -1).any()) else None,
                        seconds=round(time.time() - t0, 3))
             if monitor != "off":
-                from .evaluation import _json_safe, gap_metrics
+                from .evaluation import _json_safe, gap_metrics, split_counts
                 mon = trainer.last_monitor
-                rec.update(_json_safe({f"train_{k}": v for k, v in gap_metrics(experiment, mon["counts"]).items()}),
+                counts, joint = split_counts(mon["counts"])
+                rec.update(_json_safe({f"train_{k}": v for k, v in gap_metrics(experiment, counts, trainer.spec, joint).items()}),
                            num_faces=int(mon["counts"][0]), num_faces_total=int(mon["tables"]["generated"].shape[0]))
                 if mon["grids"]:
                     from PIL import Image
