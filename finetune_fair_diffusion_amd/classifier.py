@@ -74,69 +74,86 @@ class MobileNetV3Large:
         self.fc2 = _PW(w2, b2)
         self._ctx = None
 
-    def forward(self, chips, record=False):
-        """chips: [B,3,S,S] fp16 NCHW.  Returns logits [B, num_classes] fp16."""
+    # The recording and the non-recording forward run the SAME kernel sequence (pre-activation rounded to the working dtype, then the
+    # activation): the no-grad R1 pass that yields the dynamic targets and the R3 pass whose logits enter the loss are two evaluations of
+    # one function in the reference (:1794-1795, :1899-1903) and must agree to the bit here too -- with the activation fused into the
+    # GEMM epilogue (applied to the fp32 accumulator) only in the non-recording pass, near-tied probabilities could rank differently in the
+    # two passes and flip a target (seen at B = 8 on the random-weight test classifier).  ``record`` only decides what is KEPT.
+    @staticmethod
+    def _pw(x, lin, act, record, residual=None):
+        """1x1 conv + folded BN (+act)(+residual).  Returns (output, pre-activation or None)."""
+        if act == "none":
+            return ops.gemm(x, lin.w, bias=lin.bias, act=act, residual=residual), None
+        z = ops.gemm(x, lin.w, bias=lin.bias)
+        return ops.act_fwd(z, act), (z if record else None)
+
+    def stem_forward(self, chips, record):
+        """chips [B,3,S,S] -> (x [B*H*W, 16], H, W, record or None)."""
         B, _, H, W = chips.shape
-        ctx = [] if record else None
-
-        # The recording and the non-recording forward run the SAME kernel sequence (pre-activation rounded to the working dtype, then the
-        # activation): the no-grad R1 pass that yields the dynamic targets and the R3 pass whose logits enter the loss are two evaluations of
-        # one function in the reference (:1794-1795, :1899-1903) and must agree to the bit here too -- with the activation fused into the
-        # GEMM epilogue (applied to the fp32 accumulator) only in the non-recording pass, near-tied probabilities could rank differently in the
-        # two passes and flip a target (seen at B = 8 on the random-weight test classifier).  ``record`` only decides what is KEPT.
-        def pw(x, lin, act, residual=None):
-            """1x1 conv + folded BN (+act)(+residual).  Returns (output, pre-activation or None)."""
-            if act == "none":
-                return ops.gemm(x, lin.w, bias=lin.bias, act=act, residual=residual), None
-            z = ops.gemm(x, lin.w, bias=lin.bias)
-            return ops.act_fwd(z, act), (z if record else None)
-
         z0, H, W = ops.conv_small_cin(chips, self.stem_w, self.stem_b, B, H, W, 3, 16, 3, 2, nchw=True)
         x = ops.act_fwd(z0, "hardswish")
+        return x, H, W, (dict(z0=z0, H0=chips.shape[2], W0=chips.shape[3]) if record else None)
+
+    def block_forward(self, i, x, B, H, W, record):
+        """Inverted-residual block ``i`` on x [B*H*W, cin] -> (y [B*Ho*Wo, cout], Ho, Wo, record or None)."""
+        blk = self.blocks[i]
+        c = dict(H=H, W=W) if record else None
+        inp = x
+        act = blk["act"]
+        if blk["expand"] is not None:
+            x, z = self._pw(x, blk["expand"], act, record)
+            if record:
+                c["z_exp"] = z
+        dw = blk["dw"]
+        zd, Ho, Wo = ops.dwconv(x, dw.w, dw.bias, B, H, W, blk["exp"], dw.k, dw.stride, "none")
+        x = ops.act_fwd(zd, act)
         if record:
-            ctx.append(dict(z0=z0, H0=chips.shape[2], W0=chips.shape[3]))
-        for blk in self.blocks:
-            c = dict(H=H, W=W) if record else None
-            inp = x
-            act = blk["act"]
-            if blk["expand"] is not None:
-                x, z = pw(x, blk["expand"], act)
-                if record:
-                    c["z_exp"] = z
-            dw = blk["dw"]
-            zd, Ho, Wo = ops.dwconv(x, dw.w, dw.bias, B, H, W, blk["exp"], dw.k, dw.stride, "none")
-            x = ops.act_fwd(zd, act)
+            c["z_dw"] = zd
+        H, W = Ho, Wo
+        if blk["se"] is not None:
+            fc1, fc2 = blk["se"]
+            avg = ops.avgpool_hw(x, B, H * W, blk["exp"])
+            a1, z1 = self._pw(avg, fc1, "relu", record)
+            s, z2 = self._pw(a1, fc2, "hardsigmoid", record)
+            y = ops.scale_channels(x, s, B, H * W, blk["exp"])
             if record:
-                c["z_dw"] = zd
-            H, W = Ho, Wo
-            if blk["se"] is not None:
-                fc1, fc2 = blk["se"]
-                avg = ops.avgpool_hw(x, B, H * W, blk["exp"])
-                a1, z1 = pw(avg, fc1, "relu")
-                s, z2 = pw(a1, fc2, "hardsigmoid")
-                y = ops.scale_channels(x, s, B, H * W, blk["exp"])
-                if record:
-                    c.update(se_x=x, se_s=s, z1=z1, z2=z2)
-                x = y
-            x, _ = pw(x, blk["project"], "none", residual=inp if blk["res"] else None)
-            if record:
-                c.update(Ho=H, Wo=W)
-                ctx.append(c)
-        x, zl = pw(x, self.last, "hardswish")
+                c.update(se_x=x, se_s=s, z1=z1, z2=z2)
+            x = y
+        x, _ = self._pw(x, blk["project"], "none", record, residual=inp if blk["res"] else None)
+        if record:
+            c.update(Ho=H, Wo=W)
+        return x, H, W, c
+
+    def head_forward(self, x, B, H, W, record):
+        """x [B*H*W, 160] -> (logits [B, ncls_pad], record or None)."""
+        x, zl = self._pw(x, self.last, "hardswish", record)
         HWl = H * W
         avg = ops.avgpool_hw(x, B, HWl, 960)
-        h, zf = pw(avg, self.fc1, "hardswish")
-        logits, _ = pw(h, self.fc2, "none")
+        h, zf = self._pw(avg, self.fc1, "hardswish", record)
+        logits, _ = self._pw(h, self.fc2, "none", record)
+        return logits, (dict(zl=zl, zf=zf, HWl=HWl, B=B) if record else None)
+
+    def forward(self, chips, record=False):
+        """chips: [B,3,S,S] fp16 NCHW.  Returns logits [B, num_classes] fp16."""
+        B = chips.shape[0]
+        ctx = [] if record else None
+        x, H, W, c = self.stem_forward(chips, record)
         if record:
-            self._ctx = dict(blocks=ctx, zl=zl, zf=zf, HWl=HWl, B=B)
+            ctx.append(c)
+        for i in range(len(self.blocks)):
+            x, H, W, c = self.block_forward(i, x, B, H, W, record)
+            if record:
+                ctx.append(c)
+        logits, c = self.head_forward(x, B, H, W, record)
+        if record:
+            self._ctx = dict(blocks=ctx, **c)
         return logits[:, :self.num_classes]
 
     __call__ = forward
 
-    def backward(self, d_logits, gscale, trace=None):
-        """d_logits: [B, num_classes] fp32 = dL/dlogits.  Returns dL/dchips [B,3,S,S] fp32."""
-        c = self._ctx
-        B, blocks = c["B"], c["blocks"]
+    def head_backward(self, c, d_logits, gscale):
+        """d_logits [B, num_classes] fp32 -> the scaled fp16 gradient of the head's input [B*HWl, 160]."""
+        B = c["B"]
         dl = d_logits
         if self.ncls_pad != self.num_classes:
             dl = torch.zeros((B, self.ncls_pad), dtype=F32, device=d_logits.device)
@@ -147,32 +164,46 @@ class MobileNetV3Large:
         d = ops.gemm(d, self.fc1.wT)                                   # [B, 960] grad of the pooled features
         d = ops.avgpool_hw_bwd(d, B, c["HWl"], 960)
         d = ops.act_bwd(c["zl"], d, "hardswish")
-        d = ops.gemm(d, self.last.wT)
-        for blk in reversed(self.blocks):
-            cb = blocks.pop()
-            H, W, Ho, Wo = cb["H"], cb["W"], cb["Ho"], cb["Wo"]
-            d_res = d if blk["res"] else None
-            d = ops.gemm(d, blk["project"].wT)                          # grad wrt SE output / dw activation
-            if blk["se"] is not None:
-                fc1, fc2 = blk["se"]
-                dx, ds = ops.scale_channels_bwd(cb["se_x"], cb["se_s"], d, B, Ho * Wo, blk["exp"])
-                dz2 = ops.act_bwd(cb["z2"], ds, "hardsigmoid")
-                da1 = ops.gemm(dz2, fc2.wT)
-                dz1 = ops.act_bwd(cb["z1"], da1, "relu")
-                davg = ops.gemm(dz1, fc1.wT)
-                d = ops.avgpool_hw_bwd(davg, B, Ho * Wo, blk["exp"], add=dx)
-            d = ops.act_bwd(cb["z_dw"], d, blk["act"])
-            dw = blk["dw"]
-            d = ops.dwconv_bwd(d, dw.w, B, H, W, blk["exp"], dw.k, dw.stride)
-            if blk["expand"] is not None:
-                d = ops.act_bwd(cb["z_exp"], d, blk["act"])
-                d = ops.gemm(d, blk["expand"].wT, residual=d_res)
-            elif d_res is not None:
-                d = ops.add(d, d_res)
+        return ops.gemm(d, self.last.wT)
+
+    def block_backward(self, i, cb, d, B):
+        """The scaled fp16 gradient of block ``i``'s output -> that of its input; ``cb``: the block's record."""
+        blk = self.blocks[i]
+        H, W, Ho, Wo = cb["H"], cb["W"], cb["Ho"], cb["Wo"]
+        d_res = d if blk["res"] else None
+        d = ops.gemm(d, blk["project"].wT)                          # grad wrt SE output / dw activation
+        if blk["se"] is not None:
+            fc1, fc2 = blk["se"]
+            dx, ds = ops.scale_channels_bwd(cb["se_x"], cb["se_s"], d, B, Ho * Wo, blk["exp"])
+            dz2 = ops.act_bwd(cb["z2"], ds, "hardsigmoid")
+            da1 = ops.gemm(dz2, fc2.wT)
+            dz1 = ops.act_bwd(cb["z1"], da1, "relu")
+            davg = ops.gemm(dz1, fc1.wT)
+            d = ops.avgpool_hw_bwd(davg, B, Ho * Wo, blk["exp"], add=dx)
+        d = ops.act_bwd(cb["z_dw"], d, blk["act"])
+        dw = blk["dw"]
+        d = ops.dwconv_bwd(d, dw.w, B, H, W, blk["exp"], dw.k, dw.stride)
+        if blk["expand"] is not None:
+            d = ops.act_bwd(cb["z_exp"], d, blk["act"])
+            d = ops.gemm(d, blk["expand"].wT, residual=d_res)
+        elif d_res is not None:
+            d = ops.add(d, d_res)
+        return d
+
+    def stem_backward(self, c0, d, B, gscale):
+        d = ops.act_bwd(c0["z0"], d, "hardswish")
+        return ops.conv_small_cin_bwd(d, self.stem_w, B, c0["H0"], c0["W0"], 3, 16, 3, 2, scale=1.0 / gscale)
+
+    def backward(self, d_logits, gscale, trace=None):
+        """d_logits: [B, num_classes] fp32 = dL/dlogits.  Returns dL/dchips [B,3,S,S] fp32.  ``trace``: a list that receives the (scaled, fp16)
+        gradient at every block's input, last block first."""
+        c = self._ctx
+        B, blocks = c["B"], c["blocks"]
+        d = self.head_backward(c, d_logits, gscale)
+        for i in reversed(range(len(self.blocks))):
+            d = self.block_backward(i, blocks.pop(), d, B)
             if trace is not None:
                 trace.append(d)
-        c0 = blocks.pop()
-        d = ops.act_bwd(c0["z0"], d, "hardswish")
-        dchips = ops.conv_small_cin_bwd(d, self.stem_w, B, c0["H0"], c0["W0"], 3, 16, 3, 2, scale=1.0 / gscale)
+        dchips = self.stem_backward(blocks.pop(), d, B, gscale)
         self._ctx = None
         return dchips

@@ -36,23 +36,37 @@ class SFNet20:
         self.fc_b = sd["fc.bias"].to(dev, F32).contiguous()
         self._ctx = None
 
+    def stem_forward(self, chips):
+        """chips [N,3,S,S] -> (relu(conv) [N*H*W, C0], H, W): the direct small-Cin kernel, stride 2."""
+        N, _, H, W = chips.shape
+        return ops.conv_small_cin(chips.contiguous(), self.stem_w, self.stem_b, N, H, W, 3, self.stem_w.shape[1], 3, 2, nchw=True, act="relu")
+
+    @staticmethod
+    def down_forward(down, x, N, H, W):
+        return ops.conv3x3(x, down.wk, N, H, W, mode=ops.CONV_STRIDE2, bias=down.bias, act="relu")
+
+    @staticmethod
+    def block_forward(c1, c2, x, N, H, W):
+        """BasicBlock: relu(conv2(relu(conv1(x))) + x) -> (h, y), both post-ReLU."""
+        h, _, _ = ops.conv3x3(x, c1.wk, N, H, W, bias=c1.bias, act="relu")
+        s, _, _ = ops.conv3x3(h, c2.wk, N, H, W, bias=c2.bias, residual=x)
+        return h, ops.act_fwd(s, "relu")
+
     def forward(self, chips, record=False):
         """chips [N,3,S,S] fp16 NCHW in [-1,1] -> features [N,512] fp32 (un-normalised, one view)."""
-        N, _, H, W = chips.shape
+        N = chips.shape[0]
         ctx = [] if record else None
-        x, H, W = ops.conv_small_cin(chips.contiguous(), self.stem_w, self.stem_b, N, H, W, 3, self.stem_w.shape[1], 3, 2, nchw=True, act="relu")
+        x, H, W = self.stem_forward(chips)
         if record:
             ctx.append(("stem", x, H * 2, W * 2))
         for down, blocks in self.stages:
             if down is not None:
-                xin, Hin, Win = x, H, W
-                x, H, W = ops.conv3x3(x, down.wk, N, H, W, mode=ops.CONV_STRIDE2, bias=down.bias, act="relu")
+                Hin, Win = H, W
+                x, H, W = self.down_forward(down, x, N, H, W)
                 if record:
                     ctx.append(("down", down, x, Hin, Win))
             for c1, c2 in blocks:
-                h, _, _ = ops.conv3x3(x, c1.wk, N, H, W, bias=c1.bias, act="relu")
-                s, _, _ = ops.conv3x3(h, c2.wk, N, H, W, bias=c2.bias, residual=x)
-                y = ops.act_fwd(s, "relu")
+                h, y = self.block_forward(c1, c2, x, N, H, W)
                 if record:
                     ctx.append(("block", c1, c2, h, y, H, W))
                 x = y
@@ -63,6 +77,29 @@ class SFNet20:
 
     __call__ = forward
 
+    @staticmethod
+    def block_backward(rec, dx, N):
+        _, c1, c2, h, y, H, W = rec
+        ds = ops.act_bwd(y, dx, "relu")                                      # relu mask from the output: y > 0  <=>  s > 0
+        dh, _, _ = ops.conv3x3(ds, c2.wd, N, H, W)
+        dh = ops.act_bwd(h, dh, "relu")
+        dx, _, _ = ops.conv3x3(dh, c1.wd, N, H, W, residual=ds)              # + identity branch
+        return dx
+
+    @staticmethod
+    def down_backward(rec, dx, N):
+        _, down, y, Hin, Win = rec
+        d = ops.act_bwd(y, dx, "relu")
+        dx, H2, W2 = ops.conv3x3(d, down.wd, N, (Hin + 1) // 2, (Win + 1) // 2, mode=ops.CONV_TRANS2)
+        if (H2, W2) != (Hin, Win):       # an odd map: the transposed convolution writes 2 * ((Hin + 1) // 2) rows and columns, the last of them past the input
+            dx = dx.view(N, H2, W2, -1)[:, :Hin, :Win].reshape(N * Hin * Win, -1)
+        return dx
+
+    def stem_backward(self, rec, dx, N, gscale):
+        _, y, H0, W0 = rec
+        d = ops.act_bwd(y, dx, "relu")
+        return ops.conv_small_cin_bwd(d, self.stem_w, N, H0, W0, 3, self.stem_w.shape[1], 3, 2, scale=1.0 / gscale)
+
     def backward(self, d_f, gscale):
         """d_f [N,512] fp32 -> dL/d(chips) [N,3,S,S] fp32.  fp16 gradients carry the power-of-two ``gscale``."""
         c = self._ctx
@@ -72,19 +109,11 @@ class SFNet20:
         out = None
         for rec in reversed(c["ops"]):
             if rec[0] == "block":
-                _, c1, c2, h, y, H, W = rec
-                ds = ops.act_bwd(y, dx, "relu")                                      # relu mask from the output: y > 0  <=>  s > 0
-                dh, _, _ = ops.conv3x3(ds, c2.wd, N, H, W)
-                dh = ops.act_bwd(h, dh, "relu")
-                dx, _, _ = ops.conv3x3(dh, c1.wd, N, H, W, residual=ds)              # + identity branch
+                dx = self.block_backward(rec, dx, N)
             elif rec[0] == "down":
-                _, down, y, Hin, Win = rec
-                d = ops.act_bwd(y, dx, "relu")
-                dx, _, _ = ops.conv3x3(d, down.wd, N, (Hin + 1) // 2, (Win + 1) // 2, mode=ops.CONV_TRANS2)
+                dx = self.down_backward(rec, dx, N)
             else:
-                _, y, H0, W0 = rec
-                d = ops.act_bwd(y, dx, "relu")
-                out = ops.conv_small_cin_bwd(d, self.stem_w, N, H0, W0, 3, self.stem_w.shape[1], 3, 2, scale=1.0 / gscale)
+                out = self.stem_backward(rec, dx, N, gscale)
         self._ctx = None
         return out
 

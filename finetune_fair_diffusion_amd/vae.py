@@ -90,14 +90,27 @@ class AutoencoderKL:
         self.conv_out_wd = wo.flip(2, 3).permute(2, 3, 0, 1).reshape(9 * cfg.out_channels, boc[0]).contiguous()
         self._ctx = None
 
-    def decode_images(self, z, record=False):
-        """z: [N,4,h,w] fp32 (already divided by scaling_factor).  Returns clamp(decode(z),-1,1) as [N,3,8h,8w] fp16."""
-        cfg = self.config
+    def tail_forward(self, z):
+        """z [N,4,h,w] fp32 -> post_quant_conv (1x1) -> conv_in: the decoder's first map [N*h*w, C] fp16."""
         B, L, H, W = z.shape
-        ctx = [] if record else None
         z16 = ops.to_f16(z.contiguous())
         pq, _, _ = ops.conv_small_cin(z16, self.pq_w, self.pq_b, B, H, W, L, L, 1, 1, nchw=True)
         x, _, _ = ops.conv_small_cin(pq, self.conv_in_w, self.conv_in.bias, B, H, W, L, self.conv_in.cout, 3, 1, nchw=False)
+        return x
+
+    def head_forward(self, x, B, H, W):
+        """conv_norm_out + SiLU -> conv_out -> clamp(-1, 1) as NCHW.  Returns (img [B,3,H,W] fp16, the GroupNorm statistics, the un-clamped ``pre`` [B*H*W, 3])."""
+        cfg = self.config
+        g, st = ops.groupnorm(x, None, B, H * W, cfg.norm_num_groups, 1e-6, self.norm_out.gamma, self.norm_out.beta, True)
+        y, _, _ = ops.conv3x3(g, self.conv_out.wk, B, H, W, bias=self.conv_out.bias)
+        img = ops.nhwc_to_nchw(y, B, H * W, cfg.out_channels, out_dtype=F16, lo=-1.0, hi=1.0).view(B, cfg.out_channels, H, W)
+        return img, st, y
+
+    def decode_images(self, z, record=False):
+        """z: [N,4,h,w] fp32 (already divided by scaling_factor).  Returns clamp(decode(z),-1,1) as [N,3,8h,8w] fp16."""
+        B, L, H, W = z.shape
+        ctx = [] if record else None
+        x = self.tail_forward(z)
         x = self.mid_res[0].forward(x, None, B, H, W, None, ctx)
         x = self.mid_attn.forward(x, B, H, W, ctx)
         x = self.mid_res[1].forward(x, None, B, H, W, None, ctx)
@@ -106,9 +119,7 @@ class AutoencoderKL:
                 x = r.forward(x, None, B, H, W, None, ctx)
             if blk["up"] is not None:
                 x, H, W = ops.conv_up2(x, blk["up"], B, H, W)
-        g, st = ops.groupnorm(x, None, B, H * W, cfg.norm_num_groups, 1e-6, self.norm_out.gamma, self.norm_out.beta, True)
-        y, _, _ = ops.conv3x3(g, self.conv_out.wk, B, H, W, bias=self.conv_out.bias)
-        img = ops.nhwc_to_nchw(y, B, H * W, cfg.out_channels, out_dtype=F16, lo=-1.0, hi=1.0).view(B, cfg.out_channels, H, W)
+        img, st, y = self.head_forward(x, B, H, W)
         if record:
             self._ctx = dict(blocks=ctx, x_out=x, st_out=st, pre=y, B=B, H=H, W=W, h=z.shape[2], w=z.shape[3])
         return img
@@ -124,15 +135,28 @@ class AutoencoderKL:
         reference clamps immediately)."""
         return _Out(self.decode_images(z.to(F32)))
 
-    def backward_images(self, d_img, gscale):
-        """d_img: [N,3,H,W] fp32 = dL/d(images).  Returns dL/dz [N,4,h,w] fp32 (un-scaled)."""
-        cfg, c = self.config, self._ctx
+    def head_backward(self, c, d_img, gscale):
+        """d_img [N,3,H,W] fp32 -> the scaled fp16 gradient of the head's input [N*H*W, C]; ``c``: x_out, st_out, pre, B, H, W."""
+        cfg = self.config
         B, H, W = c["B"], c["H"], c["W"]
-        blocks = c["blocks"]
         dpre = ops.clamp_bwd(c["pre"], (d_img * gscale).contiguous().view(B, cfg.out_channels, H * W), B, H * W, cfg.out_channels)
         dg, _, _ = ops.conv_small_cin(dpre.view(B, cfg.out_channels, H, W), self.conv_out_wd, None, B, H, W, cfg.out_channels,
                                       self.conv_out.cin, 3, 1, nchw=True)
         dx, _ = ops.groupnorm_bwd(c["x_out"], None, dg, B, H * W, cfg.norm_num_groups, c["st_out"], self.norm_out.gamma, self.norm_out.beta, True)
+        return dx
+
+    def tail_backward(self, dx, B, H, W, gscale):
+        """The scaled fp16 gradient of the decoder's first map -> dL/dz [N,4,h,w] fp32, un-scaled."""
+        dpq, _, _ = ops.conv3x3(dx, self.conv_in.wd, B, H, W)  # [M, 4]
+        L = self.config.latent_channels
+        return ops.conv_small_cin_bwd(dpq, self.pq_w, B, H, W, L, L, 1, 1, scale=1.0 / gscale)
+
+    def backward_images(self, d_img, gscale):
+        """d_img: [N,3,H,W] fp32 = dL/d(images).  Returns dL/dz [N,4,h,w] fp32 (un-scaled)."""
+        c = self._ctx
+        B, H, W = c["B"], c["H"], c["W"]
+        blocks = c["blocks"]
+        dx = self.head_backward(c, d_img, gscale)
         for blk in reversed(self.ups):
             if blk["up"] is not None:
                 H, W = H // 2, W // 2
@@ -142,8 +166,6 @@ class AutoencoderKL:
         dx, _ = self.mid_res[1].backward(dx, B, H, W, blocks.pop())
         dx = self.mid_attn.backward(dx, B, H, W, blocks.pop())
         dx, _ = self.mid_res[0].backward(dx, B, H, W, blocks.pop())
-        dpq, _, _ = ops.conv3x3(dx, self.conv_in.wd, B, H, W)  # [M, 4]
-        L = cfg.latent_channels
-        dz = ops.conv_small_cin_bwd(dpq, self.pq_w, B, H, W, L, L, 1, 1, scale=1.0 / gscale)
+        dz = self.tail_backward(dx, B, H, W, gscale)
         self._ctx = None
         return dz
