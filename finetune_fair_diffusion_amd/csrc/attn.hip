@@ -836,9 +836,7 @@ extern "C" int fd_attn_fwd(const void* q, const void* k, const void* v, void* o,
 extern "C" int fd_attn_bwd_prep(const void* o, const void* d_o, float* D, int B, int H, int T, int d, void* stream) {
     FD_REQUIRE((d & 7) == 0, "fd_attn_bwd_prep: d %% 8");
     const int64_t n = (int64_t)B * T * H;
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)o, (const f16*)d_o, D, H, T, d, n);
+    hipLaunchKernelGGL(attn_bwd_prep_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)o, (const f16*)d_o, D, H, T, d, n);
     return fd_check_launch("fd_attn_bwd_prep");
 }
 

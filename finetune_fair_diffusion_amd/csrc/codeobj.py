@@ -2,8 +2,9 @@
 splits the library's .hip_fatbin into its per-translation-unit offload bundles, unbundles the gfx950 ELF of each and returns the
 disassembly and the kernel resource notes.  Used by tests/test_cpu.py to hold two build invariants: no packed-fp32 VALU instruction in any
 shipped kernel ("the round-3 hazard"), and the register / scratch budgets of the hot kernels.
-``python codeobj.py --diff OLD.so NEW.so [REGEX]`` compares two builds kernel by kernel (how a refactor shows that it left the ISA alone) and exits 1
-if any kernel symbol -- or, with REGEX, any symbol it matches -- differs or exists on one side only."""
+``python codeobj.py --diff [--renamed-ok] OLD.so NEW.so [REGEX]`` compares two builds kernel by kernel (how a refactor shows that it left the ISA
+alone) and exits 1 if any kernel symbol -- or, with REGEX, any symbol it matches -- differs or exists on one side only.  A symbol whose instructions
+are the same once register numbers are masked, with equal resource notes, is ``renamed``: it counts as a difference unless --renamed-ok is given."""
 import os
 import re
 import subprocess
@@ -126,9 +127,19 @@ def kernel_symbols(lib_path, only=None):
     return sorted(kernels)
 
 
-def diff(old_lib, new_lib, only=None):
-    """Prints, per kernel symbol, identical / differs (instruction counts, resources) / only in OLD|NEW; -> number of symbols that are not identical or
-    exist on one side only.  ``only``: a regular expression; symbols it does not match anywhere are left out of the comparison."""
+# a register operand: v12, s5, a3, v[18:21], s[4:5], a[0:15]
+_REGISTER = re.compile(r"\b[vsa](?:\d+|\[\d+:\d+\])(?![\w\[])")
+
+
+def mask_registers(text):
+    """Instruction text with every register operand replaced by one placeholder: equal for two allocations of the same instruction sequence."""
+    return _REGISTER.sub("R", text)
+
+
+def diff(old_lib, new_lib, only=None, renamed_ok=False):
+    """Prints, per kernel symbol, identical / renamed / differs (instruction counts, resources) / only in OLD|NEW; -> number of symbols that are not
+    identical or exist on one side only.  ``renamed``: same instructions once register operands are masked and the same resource notes; counted
+    unless ``renamed_ok``.  ``only``: a regular expression; symbols it does not match anywhere are left out of the comparison."""
     old, new = kernel_instructions(old_lib), kernel_instructions(new_lib)
     if only:
         old, new = ({k: v for k, v in d.items() if re.search(only, k)} for d in (old, new))
@@ -137,26 +148,31 @@ def diff(old_lib, new_lib, only=None):
         for _, co in code_objects(lib):
             for n, r in kernel_resources(co).items():
                 res[tag, n] = r
-    bad = 0
+    bad = renamed = 0
     for sym in sorted(set(old) | set(new)):
         if sym not in new or sym not in old:
             verdict = "only in OLD" if sym in old else "only in NEW"
         elif old[sym] == new[sym]:
             verdict = "identical"
+        elif mask_registers(old[sym]) == mask_registers(new[sym]) and res.get(("old", sym)) == res.get(("new", sym)):
+            verdict = "renamed"
         else:
             verdict = f"differs ({old[sym].count(chr(10)) + 1} -> {new[sym].count(chr(10)) + 1} instructions)  old {res.get(('old', sym))}  new {res.get(('new', sym))}"
-        bad += verdict != "identical"
-        print(f"{verdict:12s} {sym}" if verdict == "identical" else f"{sym}: {verdict}")
-    print(f"{len(old)} -> {len(new)} kernel symbols{f' matching {only!r}' if only else ''}, {bad} not identical or on one side only")
+        renamed += verdict == "renamed"
+        bad += verdict != "identical" and not (renamed_ok and verdict == "renamed")
+        print(f"{verdict:12s} {sym}" if verdict in ("identical", "renamed") else f"{sym}: {verdict}")
+    print(f"{len(old)} -> {len(new)} kernel symbols{f' matching {only!r}' if only else ''}, {bad} not identical or on one side only"
+          + (f"; {renamed} renamed (registers only, {'accepted' if renamed_ok else 'counted'})" if renamed else ""))
     return bad
 
 
 if __name__ == "__main__":
     import sys
     if sys.argv[1:2] == ["--diff"]:
-        if len(sys.argv) not in (4, 5):
-            sys.exit("usage: codeobj.py --diff OLD.so NEW.so [REGEX]")
-        sys.exit(1 if diff(*sys.argv[2:]) else 0)
+        args = [x for x in sys.argv[2:] if x != "--renamed-ok"]
+        if len(args) not in (2, 3):
+            sys.exit("usage: codeobj.py --diff [--renamed-ok] OLD.so NEW.so [REGEX]")
+        sys.exit(1 if diff(*args, renamed_ok="--renamed-ok" in sys.argv[2:]) else 0)
     for lib in sys.argv[1:]:
         s = packed_f32_sites(lib)
         print(f"{lib}: {len(s)} packed-fp32 VALU instructions" + (f", e.g. {s[0]}" if s else ""))

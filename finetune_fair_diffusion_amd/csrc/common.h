@@ -65,6 +65,12 @@ static inline void fd_allow_lds(size_t bytes) {
     (void)once;
 }
 
+// grid of a 1-D grid-stride launch over n work items: ceil(n / threads) blocks, at least 1 and at most ``cap`` (each caller keeps its own cap)
+static inline dim3 fd_grid_1d(int64_t n, int64_t cap, int threads = 256) {
+    const int64_t b = (n + threads - 1) / threads;
+    return dim3((unsigned)(b > cap ? cap : b < 1 ? 1 : b));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1,13 +1,6 @@
 // HBM-bound elementwise / layout kernels (16-byte fp16 vectors, grid-stride).
 #include "common.h"
 
-static inline dim3 grid_for(int64_t nvec, int threads = 256) {
-    int64_t b = (nvec + threads - 1) / threads;
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return dim3((unsigned)b);
-}
-
 // ---------------------------------------------------------------- GEGLU
 __global__ void geglu_fwd_kernel(const f16* proj, f16* y, int64_t M, int F) {
     const int FV = F >> 3;
@@ -62,17 +55,17 @@ __global__ void geglu_bwd_il_kernel(const f16* proj, const f16* dy, f16* dproj, 
 extern "C" int fd_geglu_bwd_interleaved(const void* proj, const void* dy, void* dproj, int M, int F, void* stream) {
     FD_REQUIRE((F & 3) == 0, "fd_geglu_bwd_interleaved: F %% 4");
     const int64_t n4 = (int64_t)M * (F / 4);
-    hipLaunchKernelGGL(geglu_bwd_il_kernel, grid_for(n4), dim3(256), 0, (hipStream_t)stream, (const f16*)proj, (const f16*)dy, (f16*)dproj, n4);
+    hipLaunchKernelGGL(geglu_bwd_il_kernel, fd_grid_1d(n4, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)proj, (const f16*)dy, (f16*)dproj, n4);
     return fd_check_launch("fd_geglu_bwd_interleaved");
 }
 extern "C" int fd_geglu_fwd(const void* proj, void* y, int M, int F, void* stream) {
     FD_REQUIRE((F & 7) == 0, "fd_geglu_fwd: F %% 8");
-    hipLaunchKernelGGL(geglu_fwd_kernel, grid_for((int64_t)M * (F / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)proj, (f16*)y, (int64_t)M, F);
+    hipLaunchKernelGGL(geglu_fwd_kernel, fd_grid_1d((int64_t)M * (F / 8), 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)proj, (f16*)y, (int64_t)M, F);
     return fd_check_launch("fd_geglu_fwd");
 }
 extern "C" int fd_geglu_bwd(const void* proj, const void* dy, void* dproj, int M, int F, void* stream) {
     FD_REQUIRE((F & 7) == 0, "fd_geglu_bwd: F %% 8");
-    hipLaunchKernelGGL(geglu_bwd_kernel, grid_for((int64_t)M * (F / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)proj, (const f16*)dy,
+    hipLaunchKernelGGL(geglu_bwd_kernel, fd_grid_1d((int64_t)M * (F / 8), 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)proj, (const f16*)dy,
                        (f16*)dproj, (int64_t)M, F);
     return fd_check_launch("fd_geglu_bwd");
 }
@@ -138,23 +131,23 @@ __global__ void cast_f16_f32_kernel(const f16* x, float* y, int64_t n, float sca
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = (float)x[i] * scale;
 }
 extern "C" int fd_act_fwd(const void* x, void* y, int64_t n, int act, void* stream) {
-    hipLaunchKernelGGL(act_fwd_kernel, grid_for(n / 8 + 1), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (f16*)y, n, act);
+    hipLaunchKernelGGL(act_fwd_kernel, fd_grid_1d(n / 8 + 1, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (f16*)y, n, act);
     return fd_check_launch("fd_act_fwd");
 }
 extern "C" int fd_act_bwd(const void* z, const void* dy, void* dx, int64_t n, int act, void* stream) {
-    hipLaunchKernelGGL(act_bwd_kernel, grid_for(n / 8 + 1), dim3(256), 0, (hipStream_t)stream, (const f16*)z, (const f16*)dy, (f16*)dx, n, act);
+    hipLaunchKernelGGL(act_bwd_kernel, fd_grid_1d(n / 8 + 1, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)z, (const f16*)dy, (f16*)dx, n, act);
     return fd_check_launch("fd_act_bwd");
 }
 extern "C" int fd_add(const void* a, const void* b, void* y, int64_t n, float sa, float sb, void* stream) {
-    hipLaunchKernelGGL(add_kernel, grid_for(n / 8 + 1), dim3(256), 0, (hipStream_t)stream, (const f16*)a, (const f16*)b, (f16*)y, n, sa, sb);
+    hipLaunchKernelGGL(add_kernel, fd_grid_1d(n / 8 + 1, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)a, (const f16*)b, (f16*)y, n, sa, sb);
     return fd_check_launch("fd_add");
 }
 extern "C" int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, float scale, void* stream) {
-    hipLaunchKernelGGL(cast_f32_f16_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, x, (f16*)y, n, scale);
+    hipLaunchKernelGGL(cast_f32_f16_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, x, (f16*)y, n, scale);
     return fd_check_launch("fd_cast_f32_to_f16");
 }
 extern "C" int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, float scale, void* stream) {
-    hipLaunchKernelGGL(cast_f16_f32_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const f16*)x, y, n, scale);
+    hipLaunchKernelGGL(cast_f16_f32_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)x, y, n, scale);
     return fd_check_launch("fd_cast_f16_to_f32");
 }
 
@@ -170,7 +163,7 @@ __global__ void copy_cols_kernel(const f16* src, int64_t lds, f16* dst, int64_t 
 }
 extern "C" int fd_copy_cols(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t M, int cols, void* stream) {
     FD_REQUIRE((cols & 7) == 0 && (lds & 7) == 0 && (ldd & 7) == 0, "fd_copy_cols: multiples of 8");
-    hipLaunchKernelGGL(copy_cols_kernel, grid_for(M * (cols / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)src, lds, (f16*)dst, ldd, M, cols);
+    hipLaunchKernelGGL(copy_cols_kernel, fd_grid_1d(M * (cols / 8), 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)src, lds, (f16*)dst, ldd, M, cols);
     return fd_check_launch("fd_copy_cols");
 }
 
@@ -237,7 +230,7 @@ __global__ void downsum_kernel(const f16* x, f16* y, int B, int H, int W, int C)
 
 extern "C" int fd_downsum2x2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
     FD_REQUIRE((C & 7) == 0, "fd_downsum2x2: C%%8");
-    hipLaunchKernelGGL(downsum_kernel, grid_for((int64_t)B * H * W * (C / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (f16*)y, B, H, W, C);
+    hipLaunchKernelGGL(downsum_kernel, fd_grid_1d((int64_t)B * H * W * (C / 8), 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (f16*)y, B, H, W, C);
     return fd_check_launch("fd_downsum2x2");
 }
 
@@ -334,7 +327,7 @@ __global__ void nhwc_to_nchw_kernel(const f16* x, int64_t ldx, float* y32, f16* 
 extern "C" int fd_nhwc_to_nchw(const void* x, int64_t ldx, void* y, int y_is_f32, int B, int HW, int C, float scale, float lo, float hi,
                                void* stream) {
     const int64_t n = (int64_t)B * HW * C;
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const f16*)x, ldx, y_is_f32 ? (float*)y : nullptr,
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)x, ldx, y_is_f32 ? (float*)y : nullptr,
                        y_is_f32 ? nullptr : (f16*)y, HW, C, scale, lo, hi, n);
     return fd_check_launch("fd_nhwc_to_nchw");
 }
@@ -351,7 +344,7 @@ __global__ void clamp_bwd_kernel(const f16* pre, int64_t ldx, const float* dimg,
 }
 extern "C" int fd_clamp_bwd(const void* pre, int64_t ldx, const float* dimg, float* dpre, int B, int HW, int C, float lo, float hi, void* stream) {
     const int64_t n = (int64_t)B * HW * C;
-    hipLaunchKernelGGL(clamp_bwd_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const f16*)pre, ldx, dimg, dpre, HW, C, lo, hi, n);
+    hipLaunchKernelGGL(clamp_bwd_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)pre, ldx, dimg, dpre, HW, C, lo, hi, n);
     return fd_check_launch("fd_clamp_bwd");
 }
 
@@ -371,7 +364,7 @@ __global__ void cfg_dpm_kernel(const float* eps, float g, float* lat, const floa
 }
 extern "C" int fd_cfg_dpm_step(const float* eps, float guidance, float* lat, const float* x0_prev, float* x0_out, float alpha_t, float sigma_t,
                                float c_x, float c_d0, float c_d1, int64_t n, void* stream) {
-    hipLaunchKernelGGL(cfg_dpm_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, eps, guidance, lat, x0_prev, x0_out, alpha_t, sigma_t, c_x,
+    hipLaunchKernelGGL(cfg_dpm_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, eps, guidance, lat, x0_prev, x0_out, alpha_t, sigma_t, c_x,
                        c_d0, c_d1, n);
     return fd_check_launch("fd_cfg_dpm_step");
 }
@@ -387,7 +380,7 @@ __global__ void grad_finite_scale_kernel(float* g, int64_t n, float scale, int32
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 extern "C" int fd_grad_finite_scale(float* g, int64_t n, float scale, int32_t* nonfinite_flag, void* stream) {
-    hipLaunchKernelGGL(grad_finite_scale_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, g, n, scale, nonfinite_flag);
+    hipLaunchKernelGGL(grad_finite_scale_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, g, n, scale, nonfinite_flag);
     return fd_check_launch("fd_grad_finite_scale");
 }
 // torch.optim.AdamW (decoupled decay, bias-corrected) followed by the EMA update s -= omd*(s-p)
@@ -409,7 +402,7 @@ extern "C" int fd_adamw_ema(float* p, const float* g, float* m, float* v, float*
     FD_REQUIRE(step >= 1, "fd_adamw_ema: step counts from 1");
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adamw_ema_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, bc1,
+    hipLaunchKernelGGL(adamw_ema_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, bc1,
                        bc2s, ema_one_minus_decay);
     return fd_check_launch("fd_adamw_ema");
 }
@@ -558,7 +551,7 @@ extern "C" int fd_patchify_fwd(const void* chips, void* patches, const float* me
     PatchNorm nm;
     for (int c = 0; c < 3; ++c) { nm.mean[c] = mean3[c]; nm.istd[c] = 1.f / std3[c]; }
     const int64_t n = (int64_t)N * (S / P) * (S / P) * Kp;
-    hipLaunchKernelGGL(patchify_fwd_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const f16*)chips, (f16*)patches, nm, S, P, Kp, n);
+    hipLaunchKernelGGL(patchify_fwd_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)chips, (f16*)patches, nm, S, P, Kp, n);
     return fd_check_launch("fd_patchify_fwd");
 }
 extern "C" int fd_patchify_bwd(const void* dpatches, float* dchips, const float* std3, int N, int S, int P, int Kp, float scale, int accumulate,
@@ -567,7 +560,7 @@ extern "C" int fd_patchify_bwd(const void* dpatches, float* dchips, const float*
     PatchNorm nm;
     for (int c = 0; c < 3; ++c) { nm.mean[c] = 0.f; nm.istd[c] = 1.f / std3[c]; }
     const int64_t n = (int64_t)N * 3 * S * S;
-    hipLaunchKernelGGL(patchify_bwd_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const f16*)dpatches, dchips, nm, S, P, Kp, scale, accumulate, n);
+    hipLaunchKernelGGL(patchify_bwd_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)dpatches, dchips, nm, S, P, Kp, scale, accumulate, n);
     return fd_check_launch("fd_patchify_bwd");
 }
 
@@ -583,7 +576,7 @@ __global__ void rect_scale_kernel(float* dimg, const int32_t* rects, const float
 }
 extern "C" int fd_rect_scale(float* dimg, const int32_t* rects, const float* factors, int B, int H, int W, void* stream) {
     const int64_t n = (int64_t)B * 3 * H * W;
-    hipLaunchKernelGGL(rect_scale_kernel, grid_for(n), dim3(256), 0, (hipStream_t)stream, dimg, rects, factors, H, W, n);
+    hipLaunchKernelGGL(rect_scale_kernel, fd_grid_1d(n, 4096), dim3(256), 0, (hipStream_t)stream, dimg, rects, factors, H, W, n);
     return fd_check_launch("fd_rect_scale");
 }
 

@@ -183,11 +183,6 @@ __device__ __forceinline__ void eval_grid_store(uint8_t* __restrict__ grid, int6
     }
 }
 
-static unsigned eval_grid_blocks(int64_t total) {
-    const int64_t blocks = ((total + 3) / 4 + 255) / 256;
-    return (unsigned)(blocks < 65536 ? blocks : 65536);
-}
-
 // ---------------------------------------------------------------- fd_eval_grid_u8
 // one output byte of the grid; ``idx`` = flat byte index into [rows*(H+20), cols*(W+70), 3]
 __device__ __forceinline__ uint32_t eval_grid_byte(int64_t idx, const f16* __restrict__ img, const int32_t* __restrict__ order, const int32_t* __restrict__ boxes,
@@ -223,7 +218,7 @@ extern "C" int fd_eval_grid_u8(const void* images, const int32_t* order, const i
     FD_REQUIRE(((uintptr_t)grid & 3) == 0, "fd_eval_grid_u8: the grid buffer must be 4-byte aligned");
     const int64_t total = (int64_t)rows * (H + 2 * EG_FRAME) * cols * (W + EG_STRIP + 2 * EG_FRAME) * 3;
     FD_REQUIRE(total < ((int64_t)1 << 40), "fd_eval_grid_u8: a grid of %lld bytes is not supported", (long long)total);
-    hipLaunchKernelGGL(eval_grid_kernel, dim3(eval_grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const f16*)images, order, boxes, preds, maxprob, palette,
+    hipLaunchKernelGGL(eval_grid_kernel, fd_grid_1d((total + 3) / 4, 65536), dim3(256), 0, (hipStream_t)stream, (const f16*)images, order, boxes, preds, maxprob, palette,
                        grid, N, H, W, cols, total);
     return fd_check_launch("fd_eval_grid_u8");
 }
@@ -270,8 +265,7 @@ extern "C" int fd_crop_resize_u8_fwd(const uint8_t* img, const int32_t* boxes, f
     FD_REQUIRE(B >= 1 && S >= 1 && S <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
                "fd_crop_resize_u8_fwd: B = %d (supported >= 1), S = %d, H = %d, W = %d (supported 1..4096 each)", B, S, H, W);
     const int64_t n = (int64_t)B * S * S;
-    const int64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, img, boxes, fill, (f16*)chips,
+    hipLaunchKernelGGL(crop_resize_u8_kernel, fd_grid_1d(n, 65536), dim3(256), 0, (hipStream_t)stream, img, boxes, fill, (f16*)chips,
                        H, W, S, n);
     return fd_check_launch("fd_crop_resize_u8_fwd");
 }
@@ -326,8 +320,7 @@ extern "C" int fd_warp_affine_u8_fwd(const uint8_t* img, const int32_t* src_inde
     FD_REQUIRE(n_chips >= 1 && B >= 1 && S >= 1 && S <= 4096 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
                "fd_warp_affine_u8_fwd: n_chips = %d, B = %d (supported >= 1 each), S = %d, H = %d, W = %d (supported 1..4096 each)", n_chips, B, S, H, W);
     const int64_t n = (int64_t)n_chips * S * S;
-    const int64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(warp_affine_u8_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, img, src_index, A, fill,
+    hipLaunchKernelGGL(warp_affine_u8_kernel, fd_grid_1d(n, 65536), dim3(256), 0, (hipStream_t)stream, img, src_index, A, fill,
                        (f16*)chips, (f16*)chips_mirror, B, H, W, S, n);
     return fd_check_launch("fd_warp_affine_u8_fwd");
 }
@@ -373,7 +366,7 @@ static int eval_grid_attrs_launch(const char* who, const T* images, const int32_
     FD_REQUIRE(((uintptr_t)grid & 3) == 0, "%s: the grid buffer must be 4-byte aligned", who);
     const int64_t total = (int64_t)rows * (H + 2 * EG_FRAME) * cols * (W + EG_STRIP * n_attr + 2 * EG_FRAME) * 3;
     FD_REQUIRE(total < ((int64_t)1 << 40), "%s: a grid of %lld bytes is not supported", who, (long long)total);
-    hipLaunchKernelGGL(eval_grid_attrs_kernel<T>, dim3(eval_grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, images, order, boxes, preds, bar_rows, palette, grid,
+    hipLaunchKernelGGL(eval_grid_attrs_kernel<T>, fd_grid_1d((total + 3) / 4, 65536), dim3(256), 0, (hipStream_t)stream, images, order, boxes, preds, bar_rows, palette, grid,
                        N, H, W, n_attr, cols, total);
     return fd_check_launch(who);
 }

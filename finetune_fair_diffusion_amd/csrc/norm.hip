@@ -18,6 +18,72 @@ __device__ __forceinline__ f16x8 gn_load(const GNArgs& a, int64_t pix, int c) {
     return *(const f16x8*)(a.x2 + pix * a.C2 + (c - a.C1));
 }
 
+// ---- the GroupNorm formulas, each stated once: the two-launch kernels and the single-launch kernels below only call these.  Change a formula HERE.
+// Their shapes are not free: each is the form (per element, results by value, a macro where even that was not enough) that leaves the compiled
+// kernels of all three libraries instruction-for-instruction as the written-out copies gave them (csrc/codeobj.py --diff;
+// profiles/norm_single_statement.md lists the forms that did not).
+struct GNPair { float a, b; };
+
+// (sum x, sum x^2) over n elements -> (mean, rstd)
+__device__ __forceinline__ GNPair gn_mean_rstd(float s0, float s1, float n, float eps) {
+    const float mu = s0 / n;
+    return {mu, rsqrtf(fmaxf(s1 / n - mu * mu, 0.f) + eps)};
+}
+
+// forward sums, one element (the 8-channel loop stays at the call sites: as a whole-vector helper it changed gn_reduce_kernel<0>, 441 -> 429 instructions)
+__device__ __forceinline__ void gn_sum_elem(f16 xe, float& s0, float& s1) {
+    const float x = (float)xe;
+    s0 += x;
+    s1 += x * x;
+}
+
+// y = x * sc + sh with sc = rstd * gamma, sh = beta - mean * sc.  A macro: as a function (by value, by reference or on a pointer to the pair) it
+// made the compiler commute the product in sh and renumber registers in gn_fused_fwd_kernel, which reads mean / rstd from LDS at the point of use
+#define GN_SCALE_SHIFT(sc, sh, mu, rs, gamma, beta) ((sc) = (rs) * (gamma), (sh) = (beta) - (mu) * (sc))
+
+// forward apply of one vector: y = act(x * sc + sh), rounded to the working dtype
+__device__ __forceinline__ f16x8 gn_fwd_vec(const f16x8 xv, const float (&sc)[8], const float (&sh)[8], int silu) {
+    f16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float z = (float)xv[j] * sc[j] + sh[j];
+        if (silu) z = silu_f(z);
+        o[j] = (f16)z;
+    }
+    return o;
+}
+
+// backward: the constants of channel c (sample b); per channel and by value -- filling the callers' arrays from inside moved all three backward kernels
+struct GNChan { float gm, bt, mu, rs; };
+
+__device__ __forceinline__ GNChan gn_load_params(const GNArgs& a, int b, int c, int cg) {
+    const int g = c / cg;
+    return {a.gamma[c], a.beta[c], a.mean_rstd[(b * a.G + g) * 2], a.mean_rstd[(b * a.G + g) * 2 + 1]};
+}
+
+// backward, one element: xhat and the gradient at the normalised-and-scaled value (dy taken back through the fused SiLU)
+struct GNBwdElem { float xh, dz; };
+
+__device__ __forceinline__ GNBwdElem gn_bwd_elem(f16 x, f16 dy, float gm, float bt, float mu, float rs, int silu) {
+    const float xh = ((float)x - mu) * rs;
+    float dz = (float)dy;
+    if (silu) dz *= silu_grad_f(xh * gm + bt);
+    return {xh, dz};
+}
+
+// backward result: dx = rstd * (dz * gamma - m1 - xhat * m2) + add, with m1 / m2 the group means of dz * gamma and dz * gamma * xhat
+// (a macro: as a function it kept the fp16 kernels but moved gn_bwd_apply_kernel and gn_fused_bwd_kernel of the bf16 library)
+#define GN_BWD_OUT(e, gm, rs, m1, m2, add) ((rs) * ((e).dz * (gm) - (m1) - (e).xh * (m2)) + (add))
+
+// backward: the side of the 2-source concat that the 8 channels from c0 on belong to -- its width, the channel within it, its dx and add
+// (C1 / C2 passed as values: with the GNArgs reference the two backward kernels came out with their selects scheduled differently)
+struct GNSide { int cc, Cs; f16* dxp; const f16* addp; };
+
+__device__ __forceinline__ GNSide gn_side(int c0, int C1, int C2, const f16* add1, const f16* add2, f16* dx1, f16* dx2) {
+    const bool first = c0 < C1;
+    return {first ? c0 : c0 - C1, first ? C1 : C2, first ? dx1 : dx2, first ? add1 : add2};
+}
+
 // MODE 0: per-group (sum x, sum x^2). MODE 1: per-group (sum dz*gamma, sum dz*gamma*xhat)
 template <int MODE>
 __global__ void gn_reduce_kernel(GNArgs a, float* partial /* [B,nchunks,G,2] */) {
@@ -33,11 +99,8 @@ __global__ void gn_reduce_kernel(GNArgs a, float* partial /* [B,nchunks,G,2] */)
     for (int j = 0; j < 8; ++j) {
         s0[j] = s1[j] = 0.f;
         if (MODE == 1) {
-            const int g = (c0 + j) / cg;
-            gm[j] = a.gamma[c0 + j];
-            bt[j] = a.beta[c0 + j];
-            mu[j] = a.mean_rstd[(b * a.G + g) * 2];
-            rs[j] = a.mean_rstd[(b * a.G + g) * 2 + 1];
+            const GNChan p = gn_load_params(a, b, c0 + j, cg);
+            gm[j] = p.gm; bt[j] = p.bt; mu[j] = p.mu; rs[j] = p.rs;
         }
     }
     const int r0 = chunk * a.rows_per_chunk;
@@ -64,21 +127,15 @@ __global__ void gn_reduce_kernel(GNArgs a, float* partial /* [B,nchunks,G,2] */)
             const f16x8 xv = xs[u];
             if (MODE == 0) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float x = (float)xv[j];
-                    s0[j] += x;
-                    s1[j] += x * x;
-                }
+                for (int j = 0; j < 8; ++j) gn_sum_elem(xv[j], s0[j], s1[j]);
             } else {
                 const f16x8 dv = ds[u];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float xh = ((float)xv[j] - mu[j]) * rs[j];
-                    float dz = (float)dv[j];
-                    if (a.silu) dz *= silu_grad_f(xh * gm[j] + bt[j]);
-                    const float t = dz * gm[j];
+                    const GNBwdElem e = gn_bwd_elem(xv[j], dv[j], gm[j], bt[j], mu[j], rs[j], a.silu);
+                    const float t = e.dz * gm[j];
                     s0[j] += t;
-                    s1[j] += t * xh;
+                    s1[j] += t * e.xh;
                 }
             }
         }
@@ -116,14 +173,8 @@ __device__ __forceinline__ void gn_block_stats(const GNArgs& a, const float* par
             a0 += partial[((int64_t)(b * a.nchunks + c) * a.G + g) * 2];
             a1 += partial[((int64_t)(b * a.nchunks + c) * a.G + g) * 2 + 1];
         }
-        float v0, v1;
-        if (MODE == 0) {
-            v0 = a0 / n;
-            v1 = rsqrtf(fmaxf(a1 / n - v0 * v0, 0.f) + a.eps);
-        } else {
-            v0 = a0 / n;
-            v1 = a1 / n;
-        }
+        const GNPair m = MODE == 0 ? gn_mean_rstd(a0, a1, n, a.eps) : GNPair{a0 / n, a1 / n};
+        const float v0 = m.a, v1 = m.b;
         st[g * 2] = v0;
         st[g * 2 + 1] = v1;
         if (out) { out[(b * a.G + g) * 2] = v0; out[(b * a.G + g) * 2 + 1] = v1; }
@@ -172,8 +223,8 @@ __device__ __forceinline__ void gn_block_stats_units(const GNArgs& a, const GNUn
             a0 += ps[(q * a.G + g) * 2];
             a1 += ps[(q * a.G + g) * 2 + 1];
         }
-        const float v0 = a0 / n;
-        const float v1 = rsqrtf(fmaxf(a1 / n - v0 * v0, 0.f) + a.eps);
+        const GNPair m = gn_mean_rstd(a0, a1, n, a.eps);
+        const float v0 = m.a, v1 = m.b;
         st[g * 2] = v0;
         st[g * 2 + 1] = v1;
         if (out) { out[(b * a.G + g) * 2] = v0; out[(b * a.G + g) * 2 + 1] = v1; }
@@ -198,8 +249,7 @@ __global__ void gn_apply_kernel(GNArgs a, f16* y, const float* partial, float n,
     for (int j = 0; j < 8; ++j) {
         const int g = (c0 + j) / cg;
         const float mu = st[g * 2], rs = st[g * 2 + 1];
-        sc[j] = rs * a.gamma[c0 + j];
-        sh[j] = a.beta[c0 + j] - mu * sc[j];
+        GN_SCALE_SHIFT(sc[j], sh[j], mu, rs, a.gamma[c0 + j], a.beta[c0 + j]);
     }
     const int r0 = chunk * a.rows_per_chunk;
     const int r1 = min(r0 + a.rows_per_chunk, a.HW);
@@ -215,14 +265,7 @@ __global__ void gn_apply_kernel(GNArgs a, f16* y, const float* partial, float n,
         for (int u = 0; u < GN_U; ++u) {
             const int r = rb + u * rpb;
             if (r >= r1) break;
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float z = (float)xs[u][j] * sc[j] + sh[j];
-                if (a.silu) z = silu_f(z);
-                o[j] = (f16)z;
-            }
-            *(f16x8*)(y + ((int64_t)b * a.HW + r) * C + c0) = o;
+            *(f16x8*)(y + ((int64_t)b * a.HW + r) * C + c0) = gn_fwd_vec(xs[u], sc, sh, a.silu);
         }
     }
 }
@@ -240,18 +283,12 @@ __global__ void gn_bwd_apply_kernel(GNArgs a, const float* partial, float n, con
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int g = (c0 + j) / cg;
-        gm[j] = a.gamma[c0 + j];
-        bt[j] = a.beta[c0 + j];
-        mu[j] = a.mean_rstd[(b * a.G + g) * 2];
-        rs[j] = a.mean_rstd[(b * a.G + g) * 2 + 1];
+        const GNChan p = gn_load_params(a, b, c0 + j, cg);
+        gm[j] = p.gm; bt[j] = p.bt; mu[j] = p.mu; rs[j] = p.rs;
         m1[j] = s12[g * 2];
         m2[j] = s12[g * 2 + 1];
     }
-    const bool first = c0 < a.C1;
-    const int cc = first ? c0 : c0 - a.C1;
-    const int Cs = first ? a.C1 : a.C2;
-    f16* dxp = first ? dx1 : dx2;
-    const f16* addp = first ? add1 : add2;
+    const auto [cc, Cs, dxp, addp] = gn_side(c0, a.C1, a.C2, add1, add2, dx1, dx2);
     const int r0 = chunk * a.rows_per_chunk;
     const int r1 = min(r0 + a.rows_per_chunk, a.HW);
     constexpr int GN_U = 2;      // rows in flight per thread: three streams (x, dy, add) per row
@@ -275,11 +312,8 @@ __global__ void gn_bwd_apply_kernel(GNArgs a, const float* partial, float n, con
             f16x8 o;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float xh = ((float)xs[u][j] - mu[j]) * rs[j];
-                float dz = (float)ds[u][j];
-                if (a.silu) dz *= silu_grad_f(xh * gm[j] + bt[j]);
-                const float d = rs[j] * (dz * gm[j] - m1[j] - xh * m2[j]) + (float)as[u][j];
-                o[j] = (f16)d;
+                const GNBwdElem e = gn_bwd_elem(xs[u][j], ds[u][j], gm[j], bt[j], mu[j], rs[j], a.silu);
+                o[j] = (f16)GN_BWD_OUT(e, gm[j], rs[j], m1[j], m2[j], (float)as[u][j]);
             }
             if (dxp) *(f16x8*)(dxp + ((int64_t)b * a.HW + r) * Cs + cc) = o;
         }
@@ -296,6 +330,14 @@ static int gn_geometry(int C, int HW, int& threads, int& rows_per_chunk, int& nc
     rows_per_chunk = (HW + nchunks - 1) / nchunks;
     nchunks = (HW + rows_per_chunk - 1) / rows_per_chunk;
     return 0;
+}
+
+static GNArgs gn_args(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, float eps, const float* gamma, const float* beta,
+                      int silu, const float* mean_rstd = nullptr, const void* dy = nullptr) {
+    GNArgs a = {};
+    a.x1 = (const f16*)x1; a.x2 = (const f16*)x2; a.C1 = C1; a.C2 = C2; a.B = B; a.HW = HW; a.G = groups; a.eps = eps;
+    a.gamma = gamma; a.beta = beta; a.mean_rstd = mean_rstd; a.silu = silu; a.dy = (const f16*)dy;
+    return a;
 }
 
 static int gn_check(int C1, int C2, int groups) {
@@ -326,6 +368,21 @@ static bool gn_fused_geometry(int C, int HW, int G, int maxv, GNFused& f) {
 
 // the (at most two) groups of this block that the 8 channels starting at block-local channel ``lc`` belong to
 __device__ __forceinline__ void gn_vec_groups(int lc, int cg, int& ga, int& gb) { ga = lc / cg; gb = (lc + 7) / cg; }
+
+// folds this thread's 8 per-channel sums into the (A0, A1, B0, B1) partials of those two groups and leaves them in ``red``
+__device__ __forceinline__ void gn_group_partials(const float (&s0)[8], const float (&s1)[8], int lc, int cg, float* red) {
+    int ga, gb;
+    gn_vec_groups(lc, cg, ga, gb);
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const bool first = (lc + j) / cg == ga;
+        p[first ? 0 : 2] += s0[j];
+        p[first ? 1 : 3] += s1[j];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) red[threadIdx.x * 4 + k] = p[k];
+}
 
 // sums the per-thread (A0, A1, B0, B1) group partials left in ``red`` into (sum0, sum1) of block-local group ``w`` -- called by wave w
 __device__ __forceinline__ void gn_group_total(const float* red, int w, int lane, int VB, int nact, int cg, float& t0, float& t1) {
@@ -361,24 +418,10 @@ __global__ __launch_bounds__(256) void gn_fused_fwd_kernel(GNArgs a, f16* y, flo
         if (act && i < f.nv && r < a.HW) {
             xv[i] = gn_load(a, (int64_t)b * a.HW + r, c0);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float x = (float)xv[i][j];
-                s0[j] += x;
-                s1[j] += x * x;
-            }
+            for (int j = 0; j < 8; ++j) gn_sum_elem(xv[i][j], s0[j], s1[j]);
         }
     }
-    int ga, gb;
-    gn_vec_groups(lc, cg, ga, gb);
-    float p[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const bool first = (lc + j) / cg == ga;
-        p[first ? 0 : 2] += s0[j];
-        p[first ? 1 : 3] += s1[j];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[threadIdx.x * 4 + k] = p[k];
+    gn_group_partials(s0, s1, lc, cg, red);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave < f.ngb) {
@@ -386,13 +429,13 @@ __global__ __launch_bounds__(256) void gn_fused_fwd_kernel(GNArgs a, f16* y, flo
         gn_group_total(red, wave, lane, f.VB, nact, cg, t0, t1);
         if (lane == 0) {
             const float n = (float)a.HW * (float)cg;
-            const float mu = t0 / n, rs = rsqrtf(fmaxf(t1 / n - mu * mu, 0.f) + a.eps);
-            st[wave * 2] = mu;
-            st[wave * 2 + 1] = rs;
+            const GNPair m = gn_mean_rstd(t0, t1, n, a.eps);
+            st[wave * 2] = m.a;
+            st[wave * 2 + 1] = m.b;
             if (stats_out) {
                 const int g = cb0 / cg + wave;
-                stats_out[(b * a.G + g) * 2] = mu;
-                stats_out[(b * a.G + g) * 2 + 1] = rs;
+                stats_out[(b * a.G + g) * 2] = m.a;
+                stats_out[(b * a.G + g) * 2 + 1] = m.b;
             }
         }
     }
@@ -402,22 +445,12 @@ __global__ __launch_bounds__(256) void gn_fused_fwd_kernel(GNArgs a, f16* y, flo
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int g = (lc + j) / cg;
-        sc[j] = st[g * 2 + 1] * a.gamma[c0 + j];
-        sh[j] = a.beta[c0 + j] - st[g * 2] * sc[j];
+        GN_SCALE_SHIFT(sc[j], sh[j], st[g * 2], st[g * 2 + 1], a.gamma[c0 + j], a.beta[c0 + j]);
     }
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int r = rsub + i * f.rpb;
-        if (i < f.nv && r < a.HW) {
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float z = (float)xv[i][j] * sc[j] + sh[j];
-                if (a.silu) z = silu_f(z);
-                o[j] = (f16)z;
-            }
-            *(f16x8*)(y + ((int64_t)b * a.HW + r) * C + c0) = o;
-        }
+        if (i < f.nv && r < a.HW) *(f16x8*)(y + ((int64_t)b * a.HW + r) * C + c0) = gn_fwd_vec(xv[i], sc, sh, a.silu);
     }
 }
 
@@ -434,11 +467,8 @@ __global__ __launch_bounds__(256) void gn_fused_bwd_kernel(GNArgs a, const f16* 
     float gm[8], bt[8], mu[8], rs[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int g = (c0 + j) / cg;
-        gm[j] = a.gamma[c0 + j];
-        bt[j] = a.beta[c0 + j];
-        mu[j] = a.mean_rstd[(b * a.G + g) * 2];
-        rs[j] = a.mean_rstd[(b * a.G + g) * 2 + 1];
+        const GNChan p = gn_load_params(a, b, c0 + j, cg);
+        gm[j] = p.gm; bt[j] = p.bt; mu[j] = p.mu; rs[j] = p.rs;
     }
     float s0[8], s1[8];
 #pragma unroll
@@ -450,25 +480,13 @@ __global__ __launch_bounds__(256) void gn_fused_bwd_kernel(GNArgs a, const f16* 
             const f16x8 dv = *(const f16x8*)(a.dy + pix * C + c0);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float xh = ((float)xv[j] - mu[j]) * rs[j];
-                float dz = (float)dv[j];
-                if (a.silu) dz *= silu_grad_f(xh * gm[j] + bt[j]);
-                const float t = dz * gm[j];
+                const GNBwdElem e = gn_bwd_elem(xv[j], dv[j], gm[j], bt[j], mu[j], rs[j], a.silu);
+                const float t = e.dz * gm[j];
                 s0[j] += t;
-                s1[j] += t * xh;
+                s1[j] += t * e.xh;
             }
         }
-    int ga, gb;
-    gn_vec_groups(lc, cg, ga, gb);
-    float p[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const bool first = (lc + j) / cg == ga;
-        p[first ? 0 : 2] += s0[j];
-        p[first ? 1 : 3] += s1[j];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[threadIdx.x * 4 + k] = p[k];
+    gn_group_partials(s0, s1, lc, cg, red);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave < f.ngb) {
@@ -489,11 +507,7 @@ __global__ __launch_bounds__(256) void gn_fused_bwd_kernel(GNArgs a, const f16* 
         m1[j] = st[g * 2];
         m2[j] = st[g * 2 + 1];
     }
-    const bool first = c0 < a.C1;
-    const int cc = first ? c0 : c0 - a.C1;
-    const int Cs = first ? a.C1 : a.C2;
-    f16* dxp = first ? dx1 : dx2;
-    const f16* addp = first ? add1 : add2;
+    const auto [cc, Cs, dxp, addp] = gn_side(c0, a.C1, a.C2, add1, add2, dx1, dx2);
     if (!dxp) return;
     for (int r = rsub; r < a.HW; r += f.rpb) {          // second sweep over the slab the workgroup has just read: served by L2
         const int64_t pix = (int64_t)b * a.HW + r;
@@ -504,10 +518,8 @@ __global__ __launch_bounds__(256) void gn_fused_bwd_kernel(GNArgs a, const f16* 
         f16x8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float xh = ((float)xv[j] - mu[j]) * rs[j];
-            float dz = (float)dv[j];
-            if (a.silu) dz *= silu_grad_f(xh * gm[j] + bt[j]);
-            o[j] = (f16)(rs[j] * (dz * gm[j] - m1[j] - xh * m2[j]) + (float)av[j]);
+            const GNBwdElem e = gn_bwd_elem(xv[j], dv[j], gm[j], bt[j], mu[j], rs[j], a.silu);
+            o[j] = (f16)GN_BWD_OUT(e, gm[j], rs[j], m1[j], m2[j], (float)av[j]);
         }
         *(f16x8*)(dxp + pix * Cs + cc) = o;
     }
@@ -518,9 +530,7 @@ __global__ __launch_bounds__(256) void gn_fused_bwd_kernel(GNArgs a, const f16* 
 extern "C" int fd_groupnorm_fwd(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, float eps, const float* gamma,
                                 const float* beta, int silu, void* y, float* mean_rstd, float* scratch, void* stream) {
     FD_REQUIRE(gn_check(C1, C2, groups) == 0, "fd_groupnorm_fwd: bad channels C1=%d C2=%d groups=%d", C1, C2, groups);
-    GNArgs a = {};
-    a.x1 = (const f16*)x1; a.x2 = (const f16*)x2; a.C1 = C1; a.C2 = C2; a.B = B; a.HW = HW; a.G = groups; a.eps = eps;
-    a.gamma = gamma; a.beta = beta; a.silu = silu;
+    GNArgs a = gn_args(x1, C1, x2, C2, B, HW, groups, eps, gamma, beta, silu);
     int threads;
     FD_REQUIRE(gn_geometry(C1 + C2, HW, threads, a.rows_per_chunk, a.nchunks) == 0, "fd_groupnorm: C too large");
     hipStream_t s = (hipStream_t)stream;
@@ -542,15 +552,6 @@ extern "C" int fd_groupnorm_fwd(const void* x1, int C1, const void* x2, int C2, 
 // form re-read x; here x is read once, by the pass that normalises it).
 extern "C" int fd_groupnorm_fwd_stats_p(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, float eps, const float* gamma,
                                         const float* beta, int silu, void* y, float* mean_rstd, const float* st1, int rows1, int per1,
-                                        const float* st2, int rows2, int per2, void* stream);
-extern "C" int fd_groupnorm_fwd_stats(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, float eps, const float* gamma,
-                                      const float* beta, int silu, void* y, float* mean_rstd, const float* st1, int rows1, const float* st2,
-                                      int rows2, void* stream) {
-    return fd_groupnorm_fwd_stats_p(x1, C1, x2, C2, B, HW, groups, eps, gamma, beta, silu, y, mean_rstd, st1, rows1, 0, st2, rows2, 0, stream);
-}
-
-extern "C" int fd_groupnorm_fwd_stats_p(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, float eps, const float* gamma,
-                                        const float* beta, int silu, void* y, float* mean_rstd, const float* st1, int rows1, int per1,
                                         const float* st2, int rows2, int per2, void* stream) {
     FD_REQUIRE(gn_check(C1, C2, groups) == 0, "fd_groupnorm_fwd_stats: bad channels C1=%d C2=%d groups=%d", C1, C2, groups);
     const int C = C1 + C2;
@@ -558,9 +559,7 @@ extern "C" int fd_groupnorm_fwd_stats_p(const void* x1, int C1, const void* x2, 
                C1, C2, C / groups);
     FD_REQUIRE(st1 && rows1 > 0 && HW % rows1 == 0, "fd_groupnorm_fwd_stats: rows1=%d must divide HW=%d", rows1, HW);
     FD_REQUIRE(C2 == 0 || (x2 && st2 && rows2 > 0 && HW % rows2 == 0), "fd_groupnorm_fwd_stats: rows2=%d must divide HW=%d", rows2, HW);
-    GNArgs a = {};
-    a.x1 = (const f16*)x1; a.x2 = (const f16*)x2; a.C1 = C1; a.C2 = C2; a.B = B; a.HW = HW; a.G = groups; a.eps = eps;
-    a.gamma = gamma; a.beta = beta; a.silu = silu;
+    GNArgs a = gn_args(x1, C1, x2, C2, B, HW, groups, eps, gamma, beta, silu);
     int threads;
     FD_REQUIRE(gn_geometry(C, HW, threads, a.rows_per_chunk, a.nchunks) == 0, "fd_groupnorm: C too large");
     FD_REQUIRE(threads / groups >= 1 && (threads / groups) * groups * 2 <= 1024, "fd_groupnorm_fwd_stats: %d threads for %d groups", threads, groups);
@@ -573,13 +572,17 @@ extern "C" int fd_groupnorm_fwd_stats_p(const void* x1, int C1, const void* x2, 
     return fd_check_launch("fd_groupnorm_fwd_stats");
 }
 
+extern "C" int fd_groupnorm_fwd_stats(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, float eps, const float* gamma,
+                                      const float* beta, int silu, void* y, float* mean_rstd, const float* st1, int rows1, const float* st2,
+                                      int rows2, void* stream) {
+    return fd_groupnorm_fwd_stats_p(x1, C1, x2, C2, B, HW, groups, eps, gamma, beta, silu, y, mean_rstd, st1, rows1, 0, st2, rows2, 0, stream);
+}
+
 extern "C" int fd_groupnorm_bwd(const void* x1, int C1, const void* x2, int C2, const void* dy, int B, int HW, int groups,
                                 const float* mean_rstd, const float* gamma, const float* beta, int silu, float* scratch,
                                 const void* add1, const void* add2, void* dx1, void* dx2, void* stream) {
     FD_REQUIRE(gn_check(C1, C2, groups) == 0, "fd_groupnorm_bwd: bad channels");
-    GNArgs a = {};
-    a.x1 = (const f16*)x1; a.x2 = (const f16*)x2; a.C1 = C1; a.C2 = C2; a.B = B; a.HW = HW; a.G = groups;
-    a.gamma = gamma; a.beta = beta; a.mean_rstd = mean_rstd; a.silu = silu; a.dy = (const f16*)dy;
+    GNArgs a = gn_args(x1, C1, x2, C2, B, HW, groups, 0.f, gamma, beta, silu, mean_rstd, dy);
     int threads;
     FD_REQUIRE(gn_geometry(C1 + C2, HW, threads, a.rows_per_chunk, a.nchunks) == 0, "fd_groupnorm: C too large");
     hipStream_t s = (hipStream_t)stream;
@@ -605,6 +608,12 @@ extern "C" int fd_groupnorm_bwd(const void* x1, int C1, const void* x2, int C2, 
 // the wave shuffle tree -- so the statistics are bit-identical to the one-row form (outputs too at C = 320; at wider C a few fp16 outputs move by
 // one ulp with the compiler's FMA contraction).  32768 x 320: forward 41.8 -> 17.4 us, backward 26.4 -> 18.3 us;
 // 16384 x 640: 41.9 -> 17.5 (profiles/r03_layernorm_rows_per_wave_ab.txt).  MAXV: vectors per lane (C <= 512 * MAXV).
+__device__ __forceinline__ float ln_xhat(f16 x, float mean, float rstd) { return ((float)x - mean) * rstd; }
+
+// the walk over a lane's (at most MAXV) 16-byte vectors v = lane + 64 i of a row of V vectors.  A macro: the same walk as a function template that
+// takes a lambda changed every instantiation of the kernel (fp16 forward 702 -> 668 instructions, backward 868 -> 747)
+#define LN_FOR_EACH_VEC(i, v) _Pragma("unroll") for (int i = 0; i < MAXV; ++i) if (const int v = lane + i * 64; v < V)
+
 template <bool BWD, int MAXV, int R>
 __global__ __launch_bounds__(256) void layernorm_kernel(const f16* x, const f16* dy, const float* gamma, const float* beta,
                                                         const f16* add, f16* out, float* mean_rstd, int M, int C, float eps) {
@@ -640,24 +649,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const f16* x, const f16*
         if (row >= M) break;
         float s0 = 0.f, s1 = 0.f;
         if (!BWD) {
+            LN_FOR_EACH_VEC(i, v) {
 #pragma unroll
-            for (int i = 0; i < MAXV; ++i) {
-                const int v = lane + i * 64;
-                if (v < V) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) s0 += (float)xv[r][i][j];
-                }
+                for (int j = 0; j < 8; ++j) s0 += (float)xv[r][i][j];
             }
             const float mean = wave_sum(s0) / C;
+            LN_FOR_EACH_VEC(i, v) {
 #pragma unroll
-            for (int i = 0; i < MAXV; ++i) {
-                const int v = lane + i * 64;
-                if (v < V) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float d = (float)xv[r][i][j] - mean;
-                        s1 += d * d;
-                    }
+                for (int j = 0; j < 8; ++j) {
+                    const float d = (float)xv[r][i][j] - mean;
+                    s1 += d * d;
                 }
             }
             const float rstd = rsqrtf(wave_sum(s1) / C + eps);
@@ -665,50 +666,40 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const f16* x, const f16*
                 mean_rstd[row * 2] = mean;
                 mean_rstd[row * 2 + 1] = rstd;
             }
+            LN_FOR_EACH_VEC(i, v) {
+                f16x8 o;
 #pragma unroll
-            for (int i = 0; i < MAXV; ++i) {
-                const int v = lane + i * 64;
-                if (v < V) {
-                    f16x8 o;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] = (f16)(((float)xv[r][i][j] - mean) * rstd * gm[i][j] + bt[i][j]);
-                    *(f16x8*)(out + (int64_t)row * C + v * 8) = o;
-                }
+                for (int j = 0; j < 8; ++j) o[j] = (f16)(ln_xhat(xv[r][i][j], mean, rstd) * gm[i][j] + bt[i][j]);
+                *(f16x8*)(out + (int64_t)row * C + v * 8) = o;
             }
         } else {
             const float mean = mean_rstd[row * 2], rstd = mean_rstd[row * 2 + 1];
+            LN_FOR_EACH_VEC(i, v) {
 #pragma unroll
-            for (int i = 0; i < MAXV; ++i) {
-                const int v = lane + i * 64;
-                if (v < V) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float t = (float)dv[r][i][j] * gm[i][j];
-                        s0 += t;
-                        s1 += t * ((float)xv[r][i][j] - mean) * rstd;
-                    }
+                for (int j = 0; j < 8; ++j) {
+                    const float t = (float)dv[r][i][j] * gm[i][j];
+                    s0 += t;
+                    s1 += t * ln_xhat(xv[r][i][j], mean, rstd);
                 }
             }
             const float m1 = wave_sum(s0) / C, m2 = wave_sum(s1) / C;
+            LN_FOR_EACH_VEC(i, v) {
+                f16x8 av = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (add) av = *(const f16x8*)(add + (int64_t)row * C + v * 8);
+                f16x8 o;
 #pragma unroll
-            for (int i = 0; i < MAXV; ++i) {
-                const int v = lane + i * 64;
-                if (v < V) {
-                    f16x8 av = {0, 0, 0, 0, 0, 0, 0, 0};
-                    if (add) av = *(const f16x8*)(add + (int64_t)row * C + v * 8);
-                    f16x8 o;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float xh = ((float)xv[r][i][j] - mean) * rstd;
-                        const float t = (float)dv[r][i][j] * gm[i][j];
-                        o[j] = (f16)(rstd * (t - m1 - xh * m2) + (float)av[j]);
-                    }
-                    *(f16x8*)(out + (int64_t)row * C + v * 8) = o;
+                for (int j = 0; j < 8; ++j) {
+                    const float xh = ln_xhat(xv[r][i][j], mean, rstd);
+                    const float t = (float)dv[r][i][j] * gm[i][j];
+                    o[j] = (f16)(rstd * (t - m1 - xh * m2) + (float)av[j]);
                 }
+                *(f16x8*)(out + (int64_t)row * C + v * 8) = o;
             }
         }
     }
 }
+
+#undef LN_FOR_EACH_VEC
 
 template <bool BWD>
 static void launch_layernorm(hipStream_t s, const f16* x, const f16* dy, const float* gamma, const float* beta, const f16* add, f16* out,

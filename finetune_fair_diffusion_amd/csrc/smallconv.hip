@@ -3,13 +3,6 @@
 // MobileNetV3 face-attribute classifier, and the differentiable crop+bilinear-resize of the face chip.
 #include "common.h"
 
-static inline dim3 grid1d(int64_t n, int threads = 256) {
-    int64_t b = (n + threads - 1) / threads;
-    if (b > 65535) b = 65535;
-    if (b < 1) b = 1;
-    return dim3((unsigned)b);
-}
-
 // ------------------------------------------------------------------ conv with tiny Cin (<= 8), k in {1,3}, pad (k-1)/2
 // x: [B,Cin,H,W] (nchw) or [B,H,W,Cin]; fp32 or fp16.  w: fp32 [k*k*Cin][Cout].  y: fp16 [B,Ho,Wo,Cout]
 template <typename XT>
@@ -189,10 +182,10 @@ extern "C" int fd_conv_small_cin(const void* x, int x_is_f32, int nchw, const fl
         return fd_check_launch("fd_conv_small_cin(fast)");
     }
     if (x_is_f32)
-        hipLaunchKernelGGL(conv_small_cin_kernel<float>, grid1d(n), dim3(256), 0, s, (const float*)x, nchw, w, bias, (f16*)y, B, H,
+        hipLaunchKernelGGL(conv_small_cin_kernel<float>, fd_grid_1d(n, 65535), dim3(256), 0, s, (const float*)x, nchw, w, bias, (f16*)y, B, H,
                            W, Cin, Cout, ksize, stride, Ho, Wo, act);
     else
-        hipLaunchKernelGGL(conv_small_cin_kernel<f16>, grid1d(n), dim3(256), 0, s, (const f16*)x, nchw, w, bias, (f16*)y, B, H, W,
+        hipLaunchKernelGGL(conv_small_cin_kernel<f16>, fd_grid_1d(n, 65535), dim3(256), 0, s, (const f16*)x, nchw, w, bias, (f16*)y, B, H, W,
                            Cin, Cout, ksize, stride, Ho, Wo, act);
     return fd_check_launch("fd_conv_small_cin");
 }
@@ -233,7 +226,7 @@ extern "C" int fd_conv_small_cin_bwd(const void* dy, const float* w, float* dx, 
     FD_REQUIRE(Cin >= 1 && Cin <= 8 && (ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "fd_conv_small_cin_bwd: Cin<=8, k in {1,3}");
     const int pad = (ksize - 1) / 2;
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-    hipLaunchKernelGGL(conv_small_cin_bwd_kernel, grid1d((int64_t)B * H * W), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, w, dx, B, H, W, Cin,
+    hipLaunchKernelGGL(conv_small_cin_bwd_kernel, fd_grid_1d((int64_t)B * H * W, 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, w, dx, B, H, W, Cin,
                        Cout, ksize, stride, Ho, Wo, scale);
     return fd_check_launch("fd_conv_small_cin_bwd");
 }
@@ -309,14 +302,14 @@ extern "C" int fd_dwconv_fwd(const void* x, const float* w, const float* bias, v
                              void* stream) {
     FD_REQUIRE((C & 7) == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2), "fd_dwconv_fwd: C%%8, k in {3,5}");
     const int pad = (k - 1) / 2, Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    hipLaunchKernelGGL(dwconv_fwd_kernel, grid1d((int64_t)B * Ho * Wo * (C / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)x, w, bias, (f16*)y,
+    hipLaunchKernelGGL(dwconv_fwd_kernel, fd_grid_1d((int64_t)B * Ho * Wo * (C / 8), 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)x, w, bias, (f16*)y,
                        B, H, W, C, k, stride, Ho, Wo, act);
     return fd_check_launch("fd_dwconv_fwd");
 }
 extern "C" int fd_dwconv_bwd(const void* dy, const float* w, void* dx, int B, int H, int W, int C, int k, int stride, void* stream) {
     FD_REQUIRE((C & 7) == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2), "fd_dwconv_bwd: C%%8, k in {3,5}");
     const int pad = (k - 1) / 2, Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    hipLaunchKernelGGL(dwconv_bwd_kernel, grid1d((int64_t)B * H * W * (C / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, w, (f16*)dx, B, H,
+    hipLaunchKernelGGL(dwconv_bwd_kernel, fd_grid_1d((int64_t)B * H * W * (C / 8), 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, w, (f16*)dx, B, H,
                        W, C, k, stride, Ho, Wo);
     return fd_check_launch("fd_dwconv_bwd");
 }
@@ -370,12 +363,12 @@ extern "C" int fd_avgpool_hw(const void* x, void* y, int B, int HW, int C, void*
 }
 extern "C" int fd_avgpool_hw_bwd(const void* dy, const void* add, void* dx, int B, int HW, int C, void* stream) {
     const int64_t n = (int64_t)B * HW * C;
-    hipLaunchKernelGGL(avgpool_bwd_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, (const f16*)add, (f16*)dx, HW, C, n);
+    hipLaunchKernelGGL(avgpool_bwd_kernel, fd_grid_1d(n, 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, (const f16*)add, (f16*)dx, HW, C, n);
     return fd_check_launch("fd_avgpool_hw_bwd");
 }
 extern "C" int fd_scale_channels(const void* x, const void* s, void* y, int B, int HW, int C, void* stream) {
     const int64_t n = (int64_t)B * HW * C;
-    hipLaunchKernelGGL(scale_channels_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (const f16*)s, (f16*)y, HW, C, n);
+    hipLaunchKernelGGL(scale_channels_kernel, fd_grid_1d(n, 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (const f16*)s, (f16*)y, HW, C, n);
     return fd_check_launch("fd_scale_channels");
 }
 extern "C" int fd_scale_channels_bwd(const void* x, const void* s, const void* dy, void* dx, void* ds, int B, int HW, int C, void* stream) {
@@ -458,12 +451,12 @@ __global__ void crop_resize_bwd_kernel(const float* dchips, const int32_t* boxes
 }
 extern "C" int fd_crop_resize_fwd(const void* img, const int32_t* boxes, float fill, void* chips, int B, int H, int W, int S, void* stream) {
     const int64_t n = (int64_t)B * 3 * S * S;
-    hipLaunchKernelGGL(crop_resize_fwd_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, (const f16*)img, boxes, fill, (f16*)chips, H, W, S, n);
+    hipLaunchKernelGGL(crop_resize_fwd_kernel, fd_grid_1d(n, 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)img, boxes, fill, (f16*)chips, H, W, S, n);
     return fd_check_launch("fd_crop_resize_fwd");
 }
 extern "C" int fd_crop_resize_bwd(const float* dchips, const int32_t* boxes, float* dimg, int B, int H, int W, int S, void* stream) {
     const int64_t n = (int64_t)B * 3 * H * W;       // one thread per IMAGE pixel (gather)
-    hipLaunchKernelGGL(crop_resize_bwd_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, dchips, boxes, dimg, H, W, S, n);
+    hipLaunchKernelGGL(crop_resize_bwd_kernel, fd_grid_1d(n, 65535), dim3(256), 0, (hipStream_t)stream, dchips, boxes, dimg, H, W, S, n);
     return fd_check_launch("fd_crop_resize_bwd");
 }
 
@@ -541,13 +534,13 @@ extern "C" int fd_warp_affine_fwd(const void* img, const int32_t* src_index, con
                                   int S, void* stream) {
     const int64_t n = (int64_t)n_chips * 3 * S * S;
     if (n == 0) return FD_OK;
-    hipLaunchKernelGGL(warp_affine_fwd_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, (const f16*)img, src_index, A, fill, (f16*)chips, H, W, S, n);
+    hipLaunchKernelGGL(warp_affine_fwd_kernel, fd_grid_1d(n, 65535), dim3(256), 0, (hipStream_t)stream, (const f16*)img, src_index, A, fill, (f16*)chips, H, W, S, n);
     return fd_check_launch("fd_warp_affine_fwd");
 }
 extern "C" int fd_warp_affine_bwd(const float* dchips, const int32_t* src_index, const float* A, float* dimg, int n_chips, int B, int H, int W,
                                   int S, void* stream) {
     if (n_chips == 0) return FD_OK;
     const int64_t n = (int64_t)B * 3 * H * W;       // one thread per IMAGE pixel (gather)
-    hipLaunchKernelGGL(warp_affine_bwd_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, dchips, src_index, A, dimg, n_chips, H, W, S, n);
+    hipLaunchKernelGGL(warp_affine_bwd_kernel, fd_grid_1d(n, 65535), dim3(256), 0, (hipStream_t)stream, dchips, src_index, A, dimg, n_chips, H, W, S, n);
     return fd_check_launch("fd_warp_affine_bwd");
 }

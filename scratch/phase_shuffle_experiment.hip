@@ -19,6 +19,6 @@ __global__ void phase_shuffle_kernel(const f16* __restrict__ src, f16* __restric
 }
 extern "C" int fd_phase_shuffle(const void* src, void* dst, int B, int H, int W, int C, void* stream) {
     FD_REQUIRE((C & 7) == 0, "fd_phase_shuffle: C%%8");
-    hipLaunchKernelGGL(phase_shuffle_kernel, grid_for((int64_t)B * 4 * H * W * (C / 8)), dim3(256), 0, (hipStream_t)stream, (const f16*)src, (f16*)dst, B, H, W, C);
+    hipLaunchKernelGGL(phase_shuffle_kernel, fd_grid_1d((int64_t)B * 4 * H * W * (C / 8), 4096), dim3(256), 0, (hipStream_t)stream, (const f16*)src, (f16*)dst, B, H, W, C);
     return fd_check_launch("fd_phase_shuffle");
 }

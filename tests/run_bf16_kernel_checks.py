@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BF = torch.bfloat16
-GRID = 4096 * 256          # threads of a full grid-stride launch (elementwise.hip grid_for)
+GRID = 4096 * 256          # threads of a full grid-stride launch (elementwise.hip: fd_grid_1d capped at 4096 blocks)
 
 # ============================================================================= bands
 # tests/kernel_bands.py holds the bands, generic over the 16-bit dtype; these are its bf16 bindings under the names this script has always used.
@@ -968,10 +968,33 @@ def _groupnorm_case(Bn, HW, C1, C2, silu, legacy=False):
         C(f"{tag}: bwd dx2", dx2, gref[:, C1:], 8 * 3e-3)
 
 
+def _groupnorm_second_source_case(Bn, HW, C1, C2):
+    """The second source's side of the backward (add2 into dx2; need_dx2=False: no dx2, dx1 keeps its bits) -- gate A only, 8 x the fp16 test's band."""
+    G, eps, Cc = 32, 1e-5, C1 + C2
+    tag = f"groupnorm B{Bn} HW{HW} C{C1}+{C2} add2"
+    x1 = (rnd(Bn * HW, C1, seed=1).float() * 2 + 0.5).to(BF)
+    x2 = (rnd(Bn * HW, C2, seed=2).float() - 0.3).to(BF)
+    gamma, beta = rnd(Cc, dtype=torch.float32, seed=3) * 0.2 + 1, rnd(Cc, dtype=torch.float32, seed=4) * 0.2
+    xc = torch.cat([x1, x2], 1).float().reshape(Bn, HW, Cc).permute(0, 2, 1).requires_grad_(True)
+    ref = F.silu(F.group_norm(xc, G, gamma, beta, eps))
+    dy = rnd(Bn * HW, Cc, seed=5)
+    ref.backward(dy.float().reshape(Bn, HW, Cc).permute(0, 2, 1))
+    gref = xc.grad.permute(0, 2, 1).reshape(Bn * HW, Cc)
+    _, st = ops.groupnorm(x1, x2, Bn, HW, G, eps, gamma, beta, True)
+    add1, add2 = rnd(Bn * HW, C1, seed=6), rnd(Bn * HW, C2, seed=7)
+    dx1, dx2 = ops.groupnorm_bwd(x1, x2, dy, Bn, HW, G, st, gamma, beta, True, add1=add1, add2=add2)
+    A(f"{tag}: bwd dx1", dx1, gref[:, :C1] + add1.float(), 8 * 3e-3)
+    A(f"{tag}: bwd dx2", dx2, gref[:, C1:] + add2.float(), 8 * 3e-3)
+    only1, none2 = ops.groupnorm_bwd(x1, x2, dy, Bn, HW, G, st, gamma, beta, True, add1=add1, add2=add2, need_dx2=False)
+    X(f"{tag}: need_dx2=False gives no dx2 and the same dx1 bits", none2 is None and torch.equal(only1, dx1))
+
+
 def norm_elementwise():
     for Bn, HW, C1, C2, silu in [(2, 256, 320, 0, True), (3, 64, 1280, 640, True), (2, 100, 640, 320, False)]:
         _groupnorm_case(Bn, HW, C1, C2, silu)
     _groupnorm_case(2, 1024, 320, 0, True, legacy=True)
+    for Bn, HW, C1, C2 in [(2, 64, 1280, 640), (2, 100, 640, 320), (2, 50, 64, 64)]:      # single launch twice, then reduce + apply (group width 4)
+        _groupnorm_second_source_case(Bn, HW, C1, C2)
     # from producer statistics (fd_groupnorm_fwd_stats_p through ops.groupnorm, fd_groupnorm_fwd_stats by name)
     Bn, HW, Cc, G, eps = 4, 4096, 320, 32, 1e-5
     a, w = rnd(Bn * HW, 320, seed=1), rnd(Cc, 320, scale=0.1, seed=2)

@@ -375,6 +375,25 @@ def test_codeobj_diff_counts_every_kernel_symbol(monkeypatch, capsys):
     assert codeobj.diff("old", "new", r"gemm_\w*kernel|layernorm") == 0
     assert capsys.readouterr().out.splitlines()[-1] == "2 -> 2 kernel symbols matching 'gemm_\\\\w*kernel|layernorm', 0 not identical or on one side only"
     assert codeobj.diff("old", "new", "attn|gone") == 2
+    capsys.readouterr()
+    # a third verdict, ``renamed``: the same instructions once every register operand is masked AND the same resource notes; it still counts unless accepted
+    base = "global_load_dwordx4 v[18:21], v[2:3], off\nv_fma_f32 v5, v18, s4, v6\ns_waitcnt vmcnt(0)\nv_accvgpr_read_b32 v7, a3\ns_load_dwordx2 s[4:5], s[0:1], 0x10"
+    swapped = base.replace("v[18:21]", "v[22:25]").replace("v18", "v22").replace("a3", "a1").replace("s[4:5]", "s[6:7]")
+    libs["old"] = {"gn_fused_bwd_kernel": base, "gn_apply_kernel": base, "layernorm_kernel": base, "gn_reduce_kernel": base}
+    libs["new"] = {"gn_fused_bwd_kernel": swapped, "gn_apply_kernel": base.replace("vmcnt(0)", "vmcnt(1)"), "layernorm_kernel": swapped,
+                   "gn_reduce_kernel": base.replace("v_fma_f32", "v_mul_f32")}
+    notes = {(tag, n): dict(vgpr=26, agpr=4, sgpr=16, scratch=0, lds=4096) for tag in ("old", "new") for n in libs["old"]}
+    notes["new", "layernorm_kernel"] = dict(notes["new", "layernorm_kernel"], vgpr=28)      # registers renamed AND a resource note moved: differs
+    monkeypatch.setattr(codeobj, "code_objects", lambda path: [(0, path)])
+    monkeypatch.setattr(codeobj, "kernel_resources", lambda co: {n: r for (tag, n), r in notes.items() if tag == co})
+    assert codeobj.mask_registers(base) == codeobj.mask_registers(swapped) and "s_waitcnt vmcnt(0)" in codeobj.mask_registers(base)
+    assert codeobj.diff("old", "new") == 4                      # one renamed, three differ (an operand that is no register, a resource note, an opcode)
+    out = capsys.readouterr().out
+    assert "renamed      gn_fused_bwd_kernel" in out and out.count("differs (5 -> 5 instructions)") == 3
+    assert out.splitlines()[-1] == "4 -> 4 kernel symbols, 4 not identical or on one side only; 1 renamed (registers only, counted)"
+    assert codeobj.diff("old", "new", renamed_ok=True) == 3
+    assert capsys.readouterr().out.splitlines()[-1] == "4 -> 4 kernel symbols, 3 not identical or on one side only; 1 renamed (registers only, accepted)"
+    assert codeobj.diff("old", "new", "fused", renamed_ok=True) == 0 and codeobj.diff("old", "new", "fused") == 1
 
 
 def test_library_exports_every_header_symbol():

@@ -14,7 +14,7 @@ from test_kernels_gpu import check, relerr, rnd  # noqa: F401  (same conventions
 
 pytestmark = pytest.mark.gpu
 
-GRID = 4096 * 256          # threads of a full grid-stride launch (elementwise.hip grid_for): larger sizes run a second pass
+GRID = 4096 * 256          # threads of a full grid-stride launch (elementwise.hip: fd_grid_1d capped at 4096 blocks): larger sizes run a second pass
 
 
 @pytest.fixture(scope="module")

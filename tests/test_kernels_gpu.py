@@ -293,6 +293,30 @@ def test_groupnorm(ops, dev, B, HW, C1, C2, silu):
         check("groupnorm bwd dx2", dx2, gref[:, C1:], 3e-3)
 
 
+@pytest.mark.parametrize("B,HW,C1,C2", [(2, 64, 1280, 640), (2, 100, 640, 320),          # single-launch backward (gn_fused_bwd_kernel)
+                                        (2, 50, 64, 64)])                               # group width 4 < 8: reduce + apply, 256 threads, 4 chunks of 13 rows
+def test_groupnorm_backward_second_source_add_and_skipped_dx2(ops, dev, B, HW, C1, C2):
+    """The second source's side of the backward: ``add2`` is accumulated into dx2, and with need_dx2=False no dx2 exists while dx1 keeps its bits
+    (the kernels choose source / destination per 8-channel vector: gn_side in csrc/norm.hip).  Same reference and band as test_groupnorm."""
+    G, eps, C = 32, 1e-5, C1 + C2
+    x1 = rnd(B * HW, C1, dev=dev, seed=1) * 2 + 0.5
+    x2 = rnd(B * HW, C2, dev=dev, seed=2) - 0.3
+    gamma = rnd(C, dev=dev, dtype=torch.float32, seed=3) * 0.2 + 1
+    beta = rnd(C, dev=dev, dtype=torch.float32, seed=4) * 0.2
+    xc = torch.cat([x1, x2], 1).float().reshape(B, HW, C).permute(0, 2, 1).requires_grad_(True)
+    ref = F.silu(F.group_norm(xc, G, gamma, beta, eps))
+    dy = rnd(B * HW, C, dev=dev, seed=5)
+    ref.backward(dy.float().reshape(B, HW, C).permute(0, 2, 1))
+    gref = xc.grad.permute(0, 2, 1).reshape(B * HW, C)
+    _, st = ops.groupnorm(x1, x2, B, HW, G, eps, gamma, beta, True)
+    add1, add2 = rnd(B * HW, C1, dev=dev, seed=6), rnd(B * HW, C2, dev=dev, seed=7)
+    dx1, dx2 = ops.groupnorm_bwd(x1, x2, dy, B, HW, G, st, gamma, beta, True, add1=add1, add2=add2)
+    check("groupnorm bwd dx1", dx1, gref[:, :C1] + add1.float(), 3e-3)
+    check("groupnorm bwd dx2 + add2", dx2, gref[:, C1:] + add2.float(), 3e-3)
+    only1, none2 = ops.groupnorm_bwd(x1, x2, dy, B, HW, G, st, gamma, beta, True, add1=add1, add2=add2, need_dx2=False)
+    assert none2 is None and torch.equal(only1, dx1)
+
+
 @pytest.mark.parametrize("HW,C1,C2", [(256, 1280, 0), (1024, 640, 0), (64, 1280, 1280), (4096, 320, 0)])
 def test_groupnorm_is_batch_invariant_and_reproducible(ops, dev, HW, C1, C2):
     """A sample's GroupNorm (forward, statistics, backward) must not depend on what it is batched with -- the CFG prefix path evaluates N
