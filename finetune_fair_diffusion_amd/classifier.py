@@ -4,6 +4,9 @@ with the forward that scores face chips (:1369-1371) and the explicit data-gradi
 carries dL/dlogits back to the face chips (the reference gets it from autograd through the frozen
 classifier).  Pointwise convolutions run on the MFMA GEMM, depthwise / squeeze-excite pieces on
 the direct kernels of smallconv.hip.
+
+``ZeroShotClipClassifier`` (a build addition, ``--experiment custom --classifier zero_shot``) offers the same ``forward`` / ``backward`` seam with no
+trained head: the CLIP ViT-H/14 image tower and one unit vector per class prompt, logit = logit_scale * cos(image embedding, class direction).
 """
 import torch
 
@@ -207,3 +210,52 @@ class MobileNetV3Large:
         dchips = self.stem_backward(blocks.pop(), d, B, gscale)
         self._ctx = None
         return dchips
+
+
+class ZeroShotClipClassifier:
+    """Zero-shot CLIP attribute classifier behind ``MobileNetV3Large``'s seam: ``forward(chips, record) -> logits [B, num_classes]``,
+    ``backward(d_logits, gscale) -> dL/dchips [B,3,S,S] fp32``, ``num_classes``, ``_ctx``.
+
+    ``tower``: a ``vit.VisionTransformer`` of kind "clip" that belongs to this classifier alone (``VisionTransformer.sharing(other)`` makes one on the
+    weight tensors of the regulariser's tower; the recorded forwards are never shared).  ``t_hat`` [K, E]: one direction per class prompt, the logit
+    columns in prompt order (``class_directions``); they are normalised here, in fp32.  ``logit_scale``: CLIP's ``exp(logit_scale)``.
+
+    The recording and the non-recording forward run the SAME kernel sequence -- the tower's recording one, whose GELU is a kernel of its own; its
+    non-recording forward fuses the GELU into the GEMM epilogue and differs by ~2e-3 -- so that R1's targets and R3's loss see equal bits (the comment
+    above ``MobileNetV3Large._pw``); ``record`` only decides what is kept.  The head (``ops.cosine_logits``) is fp32 with a fixed summation order."""
+
+    def __init__(self, tower, t_hat, logit_scale):
+        if tower.proj is None:
+            raise ValueError("ZeroShotClipClassifier needs a CLIP image tower (one with visual_projection)")
+        K, E = t_hat.shape
+        if E != tower.out_dim or not 1 <= K <= 16:
+            raise ValueError(f"class directions [{K}, {E}]: the tower embeds into {tower.out_dim} dimensions, and 1..16 classes are supported")
+        self.tower, self.device, self.num_classes = tower, tower.device, K
+        self.t_hat = torch.nn.functional.normalize(t_hat.to(self.device, F32), dim=-1).contiguous()
+        self.logit_scale = float(logit_scale)
+        self._ctx = None
+
+    def forward(self, chips, record=False):
+        """chips: [B,3,S,S] working dtype NCHW in [-1,1], S = the tower's image size.  Returns logits [B, num_classes] fp32."""
+        if chips.shape[2] != self.tower.config.image_size or chips.shape[3] != self.tower.config.image_size:
+            raise ValueError(f"chips of {tuple(chips.shape[2:])}: the CLIP tower takes {self.tower.config.image_size} x {self.tower.config.image_size} (--size_face)")
+        e = self.tower.forward(chips, record=True)
+        rec, self.tower._ctx = self.tower._ctx, None          # the tower object never holds a record of ours between calls
+        logits, inv_norm = ops.cosine_logits(e, self.t_hat, self.logit_scale)
+        if record:
+            self._ctx = dict(tower=rec, e=e, logits=logits, inv_norm=inv_norm)
+        return logits
+
+    __call__ = forward
+
+    def backward(self, d_logits, gscale):
+        """d_logits: [B, num_classes] fp32 = dL/dlogits.  Returns dL/dchips [B,3,S,S] fp32; the recorded forward is consumed."""
+        c, self._ctx = self._ctx, None
+        d_e = ops.cosine_logits_bwd(c["e"], self.t_hat, c["logits"], c["inv_norm"], d_logits.to(F32).contiguous(), self.logit_scale)
+        self.tower._ctx = c["tower"]
+        return self.tower.backward(d_e, gscale)
+
+
+def class_directions(text_tower, input_ids):
+    """[K, E] fp32 unit vectors on the device: ``normalize(text_embeds)`` of the tokenised class prompts ``input_ids`` [K, T] (host, int64)."""
+    return torch.nn.functional.normalize(text_tower.text_embeds(input_ids).float(), dim=-1).contiguous()

@@ -42,6 +42,14 @@ malformed value is refused here with a ValueError that names the flag, before an
   --factor1 / --factor2  one float for every attribute, or a comma list with one float per attribute
   --face_confidence_level  one float (the named experiments' ``face_*_confidence_level``)
   --asymmetric_last_attribute  exp-4's cost asymmetry for the last attribute's second class (exp-4 :1551-1556); it exists so that exp-4 can be restated
+  --classifier           mobilenet (default: the trained head behind ``--classifier_weight_path``) or zero_shot: the CLIP ViT-H/14 image tower of
+                         ``FD_CLIP_VISION_DIR`` against one text prompt per class, logit = logit_scale * cos(image embedding, prompt embedding)
+                         (classifier.ZeroShotClipClassifier) -- no trained head, ``--classifier_weight_path`` is not read; ``--size_face`` must be the
+                         tower's input size (224)
+  --class_prompts        "gender=a photo of a man|a photo of a woman;age=a photo of a young person|a photo of an old person" -- zero_shot's head:
+                         attributes separated by ``;``, class prompts by ``|`` (prompts contain commas); 1..3 attributes of 2..4 prompts.  The logit
+                         columns follow the prompts, so ``--attributes`` and ``--num_classifier_logits`` are derived (refused if given and different)
+  --zero_shot_logit_scale  zero_shot's logit scale; 0 (default) = ``exp(logit_scale)`` of the CLIP checkpoint (100 when it stores none)
 
 ``--validation`` and ``--train_monitor`` report, per attribute, ``<name>{k}_freq``, ``<name>_pred_below_0.8`` and ``<name>_gap_to_target`` (half the
 L1 distance between the class frequencies and the target) and, with two or more attributes, ``joint_gap_to_target`` over the cells.
@@ -87,8 +95,9 @@ EXPERIMENT_CLI = {
               ["face_gender_confidence_level"], dict(face_race_confidence_level=0.9), {}),
     # custom (build addition): exp-1's flags, one confidence level for whatever the attributes are, the target specification as strings.
     # factor1 / factor2 hold one float or a comma list, so they are strings here; num_classifier_logits has no default to fall back on (0 = not given)
-    "custom": (dict(factor1="0.2", factor2="0.2"), ["face_gender_confidence_level"], dict(face_confidence_level=0.9),
-               dict(attributes="", target_distribution="", target_solver="")),
+    # classifier / class_prompts / zero_shot_logit_scale: the zero-shot CLIP head (strings and a float, so the YAML overlay sets them)
+    "custom": (dict(factor1="0.2", factor2="0.2"), ["face_gender_confidence_level"], dict(face_confidence_level=0.9, zero_shot_logit_scale=0.0),
+               dict(attributes="", target_distribution="", target_solver="", classifier="mobilenet", class_prompts="")),
 }
 CUSTOM_STR_FLAGS = ("factor1", "factor2")
 
@@ -177,8 +186,9 @@ EXTRA_DEFAULTS = dict(num_denoising_steps=0, synthetic=False, face_provider="syn
                       train_monitor="off", index_font=None, index_font_size=100, log_norms=False)
 
 
-def parse_args(input_args=None, with_extras=False, experiment="exp-1", resolve=True):
-    """``resolve=False`` (``factory.default_args``): the defaults of ``custom`` without checking its specification, which is not given yet."""
+def parse_args(input_args=None, with_extras=False, experiment="exp-1", resolve=True, cfgs=None):
+    """``resolve=False`` (``factory.default_args``): the defaults of ``custom`` without checking its specification, which is not given yet.
+    ``cfgs``: the model sizes of the run (default: ``factory.SD15``, or ``TINY`` under FD_TINY), read only to check ``--size_face`` of a zero-shot run."""
     p = build_parser(experiment)
     if with_extras:
         p.add_argument("--num_denoising_steps", type=int, default=0, help="0 = draw from range(19,24) like the reference")
@@ -202,7 +212,17 @@ def parse_args(input_args=None, with_extras=False, experiment="exp-1", resolve=T
         args = argparse.Namespace(**d)
     if experiment == "custom" and resolve:      # every malformed value of the target specification is refused here
         from .fairness import experiment_spec
-        experiment_spec(experiment, args)
+        spec = experiment_spec(experiment, args)
+        if spec.zero_shot:
+            if cfgs is None:
+                from .factory import SD15, TINY
+                cfgs = TINY if os.environ.get("FD_TINY") else SD15
+            side = cfgs["clip_vision"].image_size
+            if args.size_face != side:
+                raise ValueError(f"--size_face {args.size_face}: --classifier zero_shot scores the face chips with the CLIP image tower, which takes {side} x {side}")
+            # the head is defined by the prompts: the two derived flags read as if they had been given
+            args.num_classifier_logits = spec.num_logits
+            args.attributes = ",".join(f"{n}:{c}:{k}" for n, c, k in spec.attrs)
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1 and env_local_rank != args.local_rank:
         args.local_rank = env_local_rank

@@ -48,6 +48,31 @@ def default_args(experiment="exp-1", **kw):
     return types.SimpleNamespace(**a)
 
 
+def zero_shot_classifier(spec, cfgs, sds, device, clip_model=None, gen=None):
+    """``classifier.ZeroShotClipClassifier`` of a zero-shot ``spec``.  Image tower: on the weight tensors of ``clip_model`` (the regulariser's CLIP tower)
+    when there is one, else built from ``sds['clip_vision']``; either way with recorded forwards of its own.  Class directions: the spec's prompts through
+    the ViT-H text tower (``sds['clip_text_h']``), which is freed again.  Keys that are missing are synthetic, as everywhere in ``build_trainer``: the
+    synthetic vision state of the regulariser and ``evaluate_images.synthetic_text_state`` with ``train.HashTokenizer``."""
+    from .classifier import ZeroShotClipClassifier, class_directions
+    from .evaluate_images import synthetic_text_state, tokenize_prompts
+    from .vit import VisionTransformer
+    if clip_model is not None:
+        tower = VisionTransformer.sharing(clip_model)
+        sds.pop("clip_vision", None)
+    else:
+        if "clip_vision" not in sds:
+            sds["clip_vision"] = (gen or (lambda shapes, s: W.synthetic_state_dict(shapes, seed=s)))(W.vit_param_shapes(cfgs["clip_vision"]), 9)
+        tower = VisionTransformer(cfgs["clip_vision"], sds.pop("clip_vision"), device, W.CLIP_IMAGE_MEAN, W.CLIP_IMAGE_STD)
+    synthetic = "clip_text_h" not in sds
+    text_sd = synthetic_text_state(cfgs) if synthetic else sds.pop("clip_text_h")
+    ids = tokenize_prompts(spec.prompts, cfgs["clip_text_h"], synthetic, sds.get("clip_tokenizer_dir"))
+    text_tower = CLIPTextModel(cfgs["clip_text_h"], text_sd, device)
+    t_hat = class_directions(text_tower, ids)
+    del text_tower, text_sd
+    scale = spec.logit_scale or float(sds.get("clip_logit_scale", 100.0))
+    return ZeroShotClipClassifier(tower, t_hat, scale)
+
+
 def build_trainer(args, device, cfgs=SD15, seed=0, rank=0, world_size=1, experiment="exp-1", classifier_gain=1.4, state_dicts=None,
                   frozen_copies=True, regularisers=False, lora_up_std=0.0, face_provider=None):
     """Returns (trainer, models dict).  ``state_dicts`` may carry real weights by diffusers key
@@ -60,7 +85,10 @@ def build_trainer(args, device, cfgs=SD15, seed=0, rank=0, world_size=1, experim
     (:798-818, :829-883), so the finetuned model equals the frozen original at step 0 and R1 == R2.  Only synthetic bench / smoke /
     test runs pass a non-zero std (the "one warm-up optimiser step" of SURVEY 8d) so that dL/d(down) is non-zero on the first step."""
     from .fairness import experiment_spec
-    num_classes = experiment_spec(experiment, args).num_logits
+    spec = experiment_spec(experiment, args)
+    num_classes = spec.num_logits
+    if spec.zero_shot and args.size_face != cfgs["clip_vision"].image_size:
+        raise ValueError(f"--size_face {args.size_face}: --classifier zero_shot needs the CLIP tower's input size {cfgs['clip_vision'].image_size}")
     train_prefix = experiment == "exp-2"          # prefix-token tuning: no LoRA anywhere, both networks frozen (exp-2 :946)
     if not hasattr(args, "train_unet"):           # exp-2's CLI has neither switch
         args.train_unet = False
@@ -76,7 +104,7 @@ def build_trainer(args, device, cfgs=SD15, seed=0, rank=0, world_size=1, experim
         sds["vae"] = gen(W.vae_param_shapes(cfgs["vae"]), 2)
     if "clip" not in sds:
         sds["clip"] = gen(W.clip_param_shapes(cfgs["clip"]), 3)
-    if "clf" not in sds:
+    if "clf" not in sds and not spec.zero_shot:
         sds["clf"] = gen(W.mobilenet_param_shapes(num_classes), 4, gain=classifier_gain)
     unet = UNet2DConditionModel(cfgs["unet"], sds["unet"], device)
     # exp-2 runs R1 (debiased prompt) and R2 (plain prompt) through the SAME frozen weights; a second U-Net object (its own prompt K/V cache
@@ -86,7 +114,7 @@ def build_trainer(args, device, cfgs=SD15, seed=0, rank=0, world_size=1, experim
     vae = AutoencoderKL(cfgs["vae"], sds["vae"], device)
     te = CLIPTextModel(cfgs["clip"], sds["clip"], device)
     eval_te = CLIPTextModel(cfgs["clip"], sds["clip"], device) if (args.train_text_encoder and frozen_copies) else None
-    clf = MobileNetV3Large(sds["clf"], device, num_classes)
+    clf = None if spec.zero_shot else MobileNetV3Large(sds["clf"], device, num_classes)      # zero-shot: built below, beside the CLIP tower it may share
     if args.train_unet:
         bank = unet.add_lora(args.rank, sds.get("unet_lora"), seed=seed + 5)
         if "unet_lora" not in sds and lora_up_std:   # synthetic warm-up so the up matrices are non-zero
@@ -131,6 +159,8 @@ def build_trainer(args, device, cfgs=SD15, seed=0, rank=0, world_size=1, experim
                 raise ValueError(f"{key}: encoder input {cfgs[key].image_size} != --img_size_small {args.img_size_small}")
         clip_model = VisionTransformer(cfgs["clip_vision"], sds.pop("clip_vision"), device, W.CLIP_IMAGE_MEAN, W.CLIP_IMAGE_STD)
         dino_model = VisionTransformer(cfgs["dino"], sds.pop("dino"), device, W.DINO_IMAGE_MEAN, W.DINO_IMAGE_STD)
+    if spec.zero_shot:
+        clf = zero_shot_classifier(spec, cfgs, sds, device, clip_model, gen)
     face_net = face_db = None
     if regularisers and getattr(args, "weight_loss_face", 0) != 0:
         from .sfnet import SFNet20

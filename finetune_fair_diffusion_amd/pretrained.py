@@ -127,22 +127,47 @@ def load_clip_text(model_dir, cfg):
     return _select(sd, shapes, "clip_text")
 
 
+def zero_shot_dir():
+    """``FD_CLIP_VISION_DIR`` for the zero-shot classifier, which needs it whatever the loss weights are; refused before anything is read."""
+    cdir = os.environ.get("FD_CLIP_VISION_DIR")
+    if not cdir:
+        raise FileNotFoundError("--classifier zero_shot needs FD_CLIP_VISION_DIR (CLIP ViT-H/14 directory: its checkpoint carries the image tower, the text "
+                                "tower and logit_scale, and the directory the tokenizer files); there is no hub access here (pass --synthetic for synthetic weights)")
+    return cdir
+
+
+def load_zero_shot(model_dir, cfgs):
+    """What ``classifier.ZeroShotClipClassifier`` needs from a full CLIP checkpoint directory, read once: the image tower ('clip_vision'), the text tower
+    ('clip_text_h'), ``exp(logit_scale)`` when the checkpoint stores one, else 100 ('clip_logit_scale'), and where the tokenizer lives."""
+    sd = _read([os.path.join(model_dir, "model.safetensors"), os.path.join(model_dir, "pytorch_model.bin"),
+                os.path.join(model_dir, "open_clip_pytorch_model.bin")])
+    shapes = W.clip_param_shapes(cfgs["clip_text_h"])
+    missing = [k for k in shapes if k not in sd]
+    if missing:
+        raise KeyError(f"clip_text: {model_dir} has no text tower: {missing[0]} is missing ({len(missing)} of {len(shapes)} tensors)")
+    scale = math.exp(float(sd["logit_scale"])) if "logit_scale" in sd else 100.0
+    return dict(clip_vision=_select(sd, W.vit_param_shapes(cfgs["clip_vision"]), "clip_vision"), clip_text_h=_select(sd, shapes, "clip_text"),
+                clip_logit_scale=scale, clip_tokenizer_dir=model_dir)
+
+
 def load_dino(path, cfg):
     """``dinov2_vitb14_pretrain.pth`` as torch.hub stores it (:958-961); ``mask_token`` is unused at inference and dropped."""
     sd = torch.load(path, map_location="cpu")
     return _select(sd, W.vit_param_shapes(cfg), "dino")
 
 
-def load_regularisers(args, cfgs):
+def load_regularisers(args, cfgs, have=None):
     """Weights of the loss regularisers for factory.build_trainer(state_dicts=...).  The reference fetches CLIP ViT-H/14 and DINOv2
-    from the hub caches; there is no network here, so their locations come from ``FD_CLIP_VISION_DIR`` / ``FD_DINO_WEIGHTS``."""
+    from the hub caches; there is no network here, so their locations come from ``FD_CLIP_VISION_DIR`` / ``FD_DINO_WEIGHTS``.
+    ``have``: what is loaded already; a 'clip_vision' in it (the zero-shot classifier's) is not read a second time."""
     out = {}
     if getattr(args, "weight_loss_img", 0) != 0:
         cdir, dpath = os.environ.get("FD_CLIP_VISION_DIR"), os.environ.get("FD_DINO_WEIGHTS")
         if not cdir or not dpath:
             raise FileNotFoundError("weight_loss_img != 0 needs FD_CLIP_VISION_DIR (CLIP ViT-H/14 directory) and FD_DINO_WEIGHTS "
                                     "(dinov2_vitb14_pretrain.pth); there is no hub access here (pass --synthetic for synthetic weights)")
-        out["clip_vision"] = load_clip_vision(cdir, cfgs["clip_vision"])
+        if "clip_vision" not in (have or {}):
+            out["clip_vision"] = load_clip_vision(cdir, cfgs["clip_vision"])
         out["dino"] = load_dino(dpath, cfgs["dino"])
     if getattr(args, "weight_loss_face", 0) != 0:
         out["face_net"] = load_face_net(args.opensphere_model_path, in_size=args.size_aligned_face)
@@ -157,7 +182,12 @@ def load_pretrained(args, cfgs):
     if not os.path.isdir(m):
         raise FileNotFoundError(f"{m}: not a local diffusers directory (no network here; pass --synthetic for synthetic weights)")
     experiment = getattr(args, "experiment", "exp-1")
+    spec = experiment_spec(experiment, args)
+    cdir = zero_shot_dir() if spec.zero_shot else None
     out = dict(unet=load_unet(m, cfgs["unet"]), vae=load_vae(m, cfgs["vae"]), clip=load_text_encoder(m, cfgs["clip"]))
-    out["clf"] = load_classifier(args.classifier_weight_path, experiment_spec(experiment, args).num_logits)
-    out.update(load_regularisers(args, cfgs))
+    if spec.zero_shot:          # no trained head: --classifier_weight_path is not read
+        out.update(load_zero_shot(cdir, cfgs))
+    else:
+        out["clf"] = load_classifier(args.classifier_weight_path, spec.num_logits)
+    out.update(load_regularisers(args, cfgs, have=out))
     return out

@@ -3,7 +3,9 @@
     python -m finetune_fair_diffusion_amd.train [--experiment exp-1|exp-2|exp-3|exp-4|exp-5|exp-6|custom] --config <yaml> [--synthetic]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m finetune_fair_diffusion_amd.train ...
 
-``--experiment custom`` trains towards a target distribution given by ``--attributes`` / ``--target_distribution`` / ``--target_solver`` (cli.py).
+``--experiment custom`` trains towards a target distribution given by ``--attributes`` / ``--target_distribution`` / ``--target_solver`` (cli.py);
+with ``--classifier zero_shot --class_prompts "name=prompt|prompt;..."`` the attributes are whatever the prompts describe: the CLIP image tower of
+``FD_CLIP_VISION_DIR`` scores the face chips against them and no trained classifier head is read.
 
 Same flags, YAML overlay, seeding (``set_seed(seed, device_specific=True)`` :693, prompt order from
 ``random.seed(seed+1)`` :914-921, S drawn on rank 0 from range(19,24) and broadcast :1779-1781, per-rank CPU noise
@@ -168,7 +170,7 @@ def main(argv=None, experiment=None, cfgs=None, log=None):
         pre.add_argument("--experiment", default="exp-1", choices=["exp-1", "exp-2", "exp-3", "exp-4", "exp-5", "exp-6", "custom"])
         ns, argv = pre.parse_known_args(argv)
         experiment = ns.experiment
-    args = parse_args(argv, with_extras=True, experiment=experiment)
+    args = parse_args(argv, with_extras=True, experiment=experiment, **({} if cfgs is None else dict(cfgs=cfgs)))      # a caller's model sizes: --size_face of a zero-shot run
     args.experiment = experiment
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))

@@ -92,6 +92,15 @@ class VisionTransformer:
         self.out_dim = cfg.projection_dim if clip else D
         self._ctx = None
 
+    @classmethod
+    def sharing(cls, other):
+        """A second tower on ``other``'s weight tensors (nothing is copied or loaded) with a recorded forward of its own: two users of one set of
+        frozen weights -- the image regulariser and the zero-shot classifier -- never see each other's ``_ctx``."""
+        new = cls.__new__(cls)
+        new.__dict__.update(other.__dict__)
+        new._ctx = None
+        return new
+
     # ------------------------------------------------------------------ forward
     def forward(self, chips, record=False):
         """chips [N,3,S,S] fp16 NCHW in [-1,1] (already resized).  Returns the raw embedding [N, out_dim] fp32."""

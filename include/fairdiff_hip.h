@@ -344,6 +344,20 @@ int fd_crop_resize_fwd(const void* img, const int32_t* boxes, float fill, void* 
 int fd_crop_resize_bwd(const float* dchips /* [B,3,S,S] */, const int32_t* boxes, float* dimg /* [B,3,H,W] (+=) */,
                        int B, int H, int W, int S, void* stream);
 
+/* ---- zero-shot CLIP classifier head (classifier.ZeroShotClipClassifier; a build addition, the reference has no counterpart).  fp32 throughout: the same
+ * code in both libraries.  Additive: FD_ABI_VERSION is unchanged.
+ * e [N, E] raw image embeddings with row stride lde >= E; t_hat [K, E] unit class directions, rows contiguous:
+ *     inv_norm[n]  = 1 / max(|e_n|, 1e-12)                      (an all-zero row gives logits 0 and gradient 0)
+ *     logits[n, k] = scale * inv_norm[n] * <e_n, t_hat_k>       logits [N, K] and inv_norm [N] contiguous
+ * and, with c = logits / scale (0 when scale is 0) and e^ = e * inv_norm,
+ *     d_e[n] = scale * inv_norm[n] * (sum_k d_logits[n, k] t_hat_k - (sum_k d_logits[n, k] c[n, k]) e^_n)        d_logits [N, K], d_e [N, E] contiguous
+ * the gradient of the logits with respect to e; a row at the clamp (inv_norm[n] >= 5e11: it has no direction) gets d_e[n] = 0.  Rows are independent; every sum runs in one fixed order (a function of E and K),
+ * no atomics: two calls on the same data return the same bits on any stream.  Pointers need 4-byte alignment only.  N >= 1, E 1..4096, K 1..16.
+ * Refused on the host with FD_ERR_ARG before anything is launched: a null buffer, N < 1, E or K outside their range, lde < E. */
+int fd_cosine_logits_fwd(const float* e, int64_t lde, const float* t_hat, float scale, float* logits, float* inv_norm, int N, int E, int K, void* stream);
+int fd_cosine_logits_bwd(const float* e, int64_t lde, const float* t_hat, const float* logits, const float* inv_norm, const float* d_logits, float scale,
+                         float* d_e, int N, int E, int K, void* stream);
+
 /* ---- image-semantics regularisers (get_clip_feat / get_dino_feat, exp-1 1-main-debias.py:1139-1175; Resize :1860,1905).
  * chips [N,3,S,S] fp16 NCHW in [-1,1] -> patches [N*(S/P)^2, Kp] fp16 = ((x+1)/2 - mean_c)/std_c in Conv2d(3,D,P,P) weight order
  * (k = c*P*P + py*P + px), zero-padded to Kp; the patch embedding is then a GEMM.  bwd: dchips fp32 (+)= 0.5/std_c*scale*dpatches */
