@@ -869,7 +869,7 @@ extern "C" int fd_attn_bwd_dkdv(const void* q, const void* k, const void* v, con
     FD_REQUIRE((ldq & 7) == 0 && (ldkv & 7) == 0 && (lddkv & 3) == 0, "fd_attn_bwd_dkdv: row strides");
     FD_REQUIRE(attn_shape_ok(B, H, Tq, Tk, Tkr, kv_div), "fd_attn_bwd_dkdv: bad shape");
     const dim3 grid(((Tk + 127) / 128) * H * B);
-    // accumulate == 2: fp32 per-sample slabs instead of atomics (dk, dv: [kv_div][Bk*Tkr][lddkv] fp32, every element written)
+    // accumulate == 2: fp32 per-sample slabs instead of atomics (dk, dv: [kv_div][Bk*Tkr][lddkv] fp32; the Tk key rows x H*d columns of every item written, pad rows and gap columns untouched)
     const int64_t slab = accumulate == 2 ? (int64_t)(B / kv_div) * Tkr * lddkv : 0;
     FD_REQUIRE(accumulate != 2 || (B % kv_div) == 0, "fd_attn_bwd_dkdv: B must be a multiple of kv_div");
     // scale < 0: q arrives multiplied by |scale| * log2(e) ("pre-scaled q"): dK = scale * dS^T . q = dS^T . q' / log2(e)

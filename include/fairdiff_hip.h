@@ -12,6 +12,29 @@
  * mutable state except the thread-local last-error string).  Activations are fp16
  * ("wd" in SURVEY 8a), channels-last: an image tensor is [B, H, W, C] == a token matrix
  * [B*H*W, C]; LoRA/optimizer state and all reductions are fp32.
+ *
+ * Alignment.  Entry points added later state theirs where they are declared.  For the kernels of the training step the requirement of an operand is the
+ * widest load / store its kernel issues on it (bytes; "16-bit" = the working dtype; a row stride must keep every row on the same alignment).  Nothing is
+ * checked on the host unless stated; tests/test_kernels_guard_gpu.py runs every operand at exactly this alignment (address = a modulo 2a) and no more.
+ *   fd_attn_fwd                 q, k, v 16 (ldq, ldk %% 8); o 8; lse 4
+ *   fd_attn_bwd_prep            o, d_o 16 (d %% 8); D 4
+ *   fd_attn_bwd_dq              q, k, v, d_o, o 16; lse, D 4; dq 8 (lddq %% 4)
+ *   fd_attn_bwd_dkdv            q, k, v, d_o 16; lse, D 4; dk, dv: 8 as 16-bit (accumulate 0, kv_div 1), 4 as fp32 atomics, 16 as fp32 slabs (accumulate 2); lddkv %% 4
+ *   fd_sum_slabs                in, out 16; n %% 4 == 0 (refused otherwise)
+ *   fd_cross_attn_block         x, wq, wo, k, y, yn, n2_out, q_out, o_out, lora_*_down, lora_*_up 16 (ld_* %% 8); vt 8 (Lp %% 4); tq_out, to_out 8; bo 16;
+ *                               ln2_* / ln3_* gamma and beta, ln2_stats, yn_stats, lse_out 4
+ *   fd_small_attn_fwd / _bwd    q, k, v, o, d_o, dq, dk, dv 2; P 4; key_valid 4
+ *   fd_groupnorm_fwd / _bwd     x1, x2, y, dy, add1, add2, dx1, dx2 16 (C1, C2 %% 8); gamma, beta, mean_rstd, scratch 4
+ *   fd_groupnorm_fwd_stats(_p)  the same; st1, st2 8
+ *   fd_layernorm_fwd / _bwd     x, y, dy, add, dx 16 (C %% 8); gamma, beta, mean_rstd 4
+ *   fd_geglu_fwd / _bwd         proj, y, dy, dproj 16 (F %% 8);  fd_geglu_bwd_interleaved: proj, dproj 16, dy 8 (F %% 4)
+ *   fd_act_fwd / _bwd, fd_add   every operand 16, any n (the last n %% 8 elements are read and written one by one)
+ *   fd_cast_f32_to_f16 / fd_cast_f16_to_f32, fd_nhwc_to_nchw, fd_clamp_bwd, fd_softmax_rows(_bwd)     element size: 2 for 16-bit, 4 for fp32 operands, any stride
+ *   fd_copy_cols, fd_transpose_btc, fd_downsum2x2     every operand 16 (cols, lds, ldd, C, Tp, ldx %% 8)
+ *   fd_lora_wgrad               T 16 (ldt %% 8); G, scratch 4; X 16 where N and ldx are multiples of 8 at R <= 8, 8 where they are multiples of 4 at 9 <= R <= 16
+ *                               (the vectorised kernels), else 2
+ *   fd_lora_wgrad_multi         T 16; G 4; X 16 (R <= 8), 8 (9 <= R <= 16), 16 (R >= 17: checked, with T); scratch 4 (R <= 16), 16 (R >= 17)
+ *   fd_cfg_dpm_step, fd_grad_finite_scale, fd_adamw_ema     every operand 4
  */
 #ifndef FAIRDIFF_HIP_H
 #define FAIRDIFF_HIP_H
@@ -191,7 +214,9 @@ int fd_attn_bwd_dq(const void* q, const void* k, const void* v, const void* d_o,
  * ``accumulate`` == 1 selects the fp32-atomic form at kv_div == 1 too: several launches -- timesteps of the truncated chain whose
  * backwards run on different HIP streams -- may then add into one accumulator concurrently.
  * ``accumulate`` == 2 (round 4, what the training step uses): NO atomics -- dk / dv are fp32 [kv_div][Bk*Tkr][lddkv] and sample j of every
- * K/V group WRITES slab j; fd_sum_slabs then adds the slabs in a fixed order: shared dK / dV are bit-reproducible. */
+ * K/V group WRITES slab j; fd_sum_slabs then adds the slabs in a fixed order: shared dK / dV are bit-reproducible.
+ * What is written, all three forms: the Tk key rows of every K/V item, columns 0 .. H*d of a row.  The pad rows Tk..Tkr of an item and the columns
+ * behind H*d of a strided row are never touched (nor read from k / v): a caller that sums or reads padded buffers clears them once itself. */
 int fd_attn_bwd_dkdv(const void* q, const void* k, const void* v, const void* d_o,
                      const float* lse, const float* D, void* dk, void* dv, int B, int H, int Tq, int Tk, int Tkr, int d,
                      int kv_div, float scale, int ldq, int ldkv, int lddkv, int accumulate, void* stream);
